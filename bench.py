@@ -11,13 +11,25 @@ are independent: strong scaling, no data-path collective); a gloo barrier bracke
 region and the max elapsed time over ranks is used.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--mode inplace|compact]
-                  [--rotate R]
+                  [--rotate R] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, the K
+timed steps, the result line.  Its `roofline` comes from the HIP events the timed steps
+themselves bracket every 10th payload kernel with (none sampled: the step time, an upper bound).
+--full adds every measurement that takes runs of its own: the CPU baseline, C5 on one GPU, the
+event window, the copy ceiling, the device timeline and (with --e2e) the host-memory paths.
+
+--dump-outputs DIR writes what the last timed step left a caller of the decode (or build) call,
+right after the timed steps, as DIR/<name>.npy (DIR/rank<r>/ with more than one rank): every
+output buffer byte for byte in float32 (offsets in float64), a seeded sample of the elements
+where a buffer is larger than 8 MB as written.  Inputs are generated from a fixed seed, so two
+builds run with the same arguments can be compared file for file.
 
 --config c5 runs BASELINE config C5 instead: 8 388 608 x 64 KiB frames in total, split into
 contiguous per-rank shards (strong scaling), each decoded in resident 1 048 576-frame passes.
 It is the default whenever more than one GPU runs (BASELINE config 5, "reported at 1/2/4/8
-GPUs"); the N=1 default (C3) also times C5 on its one GPU ("c5_1gpu", and "c5_base": that
-value in the N>1 lines' unit) so the curve has a base.
+GPUs"); with --full the N=1 default (C3) also times C5 on its one GPU ("c5_1gpu", and
+"c5_base": that value in the N>1 lines' unit) so the curve has a base.
 
 --rotate R decodes R independent copies of the batch round-robin (one per step), so a step's
 wire was last touched R-1 steps earlier: with R copies larger than the 256 MB Infinity Cache
@@ -28,8 +40,8 @@ directly with --gpus N > 1, this process spawns the N rank processes itself (bef
 touches a GPU), waits for them and prints rank 0's line.
 
 Rank 0 prints ONE JSON line.  `roofline` comes from HIP events bracketing the payload kernel
-on its stream during the timed steps; `cpu_baseline` times the CPU port of the reference path
-(oracle/, test infrastructure) on this host, rank 0 at N=1 only.
+on its stream during the timed steps; with --full, `cpu_baseline` times the CPU port of the
+reference path (oracle/, test infrastructure) on this host, rank 0 at N=1 only.
 """
 import argparse
 import ctypes as C
@@ -344,6 +356,9 @@ class StubWorkload:
         if os.environ.get("UVHTTP_WS_STUB_FAIL_RANK") == os.environ.get("RANK", "0"):
             raise SystemExit("stub decode failed")
 
+    def outputs(self):
+        return {}
+
     def close(self):
         pass
 
@@ -580,6 +595,29 @@ class GpuWorkload:
             if s["n_delivered"] != n or s["status"] != 0:
                 raise SystemExit(f"decode failed: {s}")
 
+    def outputs(self):
+        """What the last pass left its caller, {name: device tensor}, each cut to the bytes the
+        call defines (the buffers are allocated with slack, and the arena, the message list and
+        the built frames end where the summary / the last offset says)."""
+        n = self.n
+        if self.build_dev is not None:
+            return {"frames": self.build_out[: int(self.build_off[n].item())],
+                    "frame_off": self.build_off}
+        if self.streams_dev is not None:
+            return {"wire": self.wire[: self.wire_len], "desc": self.s_desc[: n * 32],
+                    "results": self.s_res}
+        out = {"summary": self.summ}
+        if not self.no_desc:
+            out["desc"] = self.desc[: n * 32]
+        if self.arena is None:
+            out["wire"] = self.wire[: self.wire_len]
+        else:
+            s = self.eng.read_summary(self.summ)
+            out["arena"] = self.arena[: s["arena_bytes"]]
+            # entry [n_messages] describes the message still open, when one is
+            out["msgs"] = self.msgs[: (s["n_messages"] + (1 if s["pending_bytes"] else 0)) * 32]
+        return out
+
     def close(self):
         self.eng.close()
         for k in ("wire", "wires", "desc", "summ", "arena", "msgs", "build_src", "build_out",
@@ -626,6 +664,27 @@ def summarize_stamps(recs):
             "gaps_mean_us": {k: mean(v) for k, v in gaps.items()},
             "gaps_max_us": {k: round(max(v) / 1e3, 2) for k, v in gaps.items()},
             "source": "device wall clock (uvhttp_ws_gpu_engine_read_stamps), medians unless named"}
+
+
+DUMP_ARRAY_BYTES = 8 << 20  # per .npy file; a run writes at most 4 (compact), under 64 MB in all
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every output of the last timed step as path/<name>.npy — bytes as
+    float32, offsets as float64 (both exact).  An array that would exceed DUMP_ARRAY_BYTES is
+    cut to that many of its elements, at sorted indices drawn from SEED (the same ones in
+    every run of the same arguments)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.reshape(-1)
+        dt = np.float32 if t.dtype == torch.uint8 else np.float64
+        keep = DUMP_ARRAY_BYTES // np.dtype(dt).itemsize
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(SEED).integers(0, t.numel(), size=keep))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(dt))
 
 
 def timed_run(wl, steps, warmup, world):
@@ -689,6 +748,12 @@ def main():
     ap.add_argument("--conns", type=int, default=0,
                     help="streams mode: connections the frames are split over "
                          "(default: one frame per connection, 4096 for c4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, C5 "
+                         "on one GPU, the event window, the copy ceiling, the device timeline, "
+                         "--e2e (the --no-* options below take single ones out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5-base", action="store_true",
                     help="N=1: skip the extra C5-on-one-GPU measurement")
@@ -710,6 +775,10 @@ def main():
                          "(launcher readiness runs on a one-GPU box; the ranks share one HBM)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # launcher tests
     args = ap.parse_args()
+    if not args.full:
+        if args.e2e:
+            ap.error("--e2e is one of the extra measurements: give --full with it")
+        args.no_cpu_baseline = args.no_c5_base = args.no_ceiling = args.no_stamps = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the parent never touches HIP (nor imports torch): it only counts devices from the
@@ -741,7 +810,11 @@ def main():
     wl.no_stamps = args.no_stamps
     el_max, k_ms, k_n = timed_run(wl, args.steps, args.warmup, world)
     timed_launches = k_n
-    if rank == 0 and hasattr(wl, "event_window") and k_n < MIN_EVENT_LAUNCHES and wl.graph is None:
+    if args.dump_outputs:  # before anything below runs the decode again
+        dump_outputs(args.dump_outputs if world == 1 else
+                     os.path.join(args.dump_outputs, f"rank{rank}"), wl.outputs())
+    if args.full and rank == 0 and hasattr(wl, "event_window") and k_n < MIN_EVENT_LAUNCHES \
+            and wl.graph is None:
         w_ms, w_n = wl.event_window(MIN_EVENT_LAUNCHES - k_n)
         k_ms, k_n = k_ms + w_ms, k_n + w_n
     n, plen, passes, stride = wl.n, wl.plen, wl.passes, wl.stride

@@ -115,7 +115,15 @@ def test_visible_gpus_without_hip(monkeypatch):
     for v in ("ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         monkeypatch.delenv(v, raising=False)
     assert bench.visible_gpus() >= 0  # KFD topology (0 in a container without a GPU)
-    assert "torch" not in sys.modules or not sys.modules["torch"].cuda.is_initialized()
+    # in a process of its own: this one may hold a GPU already (an earlier test's engine)
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, bench; assert bench.visible_gpus() >= 0; t = sys.modules.get('torch'); "
+            "assert t is None or not t.cuda.is_initialized(); "
+            "assert not bench.parent_touched_gpu()")
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
+                       cwd=repo)
+    assert p.returncode == 0, p.stderr
 
 
 def test_bench_torchrun_form_single_process():

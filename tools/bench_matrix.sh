@@ -7,7 +7,7 @@ OUT=gpurun_out/bench_matrix_${TAG:-r01}.jsonl
 for cfg in c3 c2 c4; do
   for mm in ${MODES:-inplace inplace:nd compact compact:nd streams build build_masked}; do
     IFS=: read mode nd <<< "$mm"
-    timeout -k 10 300 python bench.py --config $cfg --mode $mode ${nd:+--no-desc} --steps ${STEPS:-100} --warmup 10 \
+    timeout -k 10 300 python bench.py --full --config $cfg --mode $mode ${nd:+--no-desc} --steps ${STEPS:-100} --warmup 10 \
       --no-cpu-baseline >> "$OUT" 2>> gpurun_out/bench_matrix.err || { echo "fail $cfg $mode"; exit 1; }
   done
 done

@@ -52,7 +52,7 @@ if has smoke; then
   tail -1 ${O}_smoke.log
 fi
 if has bench; then
-  timeout -k 10 600 python -u bench.py > ${O}_bench.json 2> ${O}_bench.err
+  timeout -k 10 600 python -u bench.py --full > ${O}_bench.json 2> ${O}_bench.err
   cut -c1-600 ${O}_bench.json
 fi
 if has matrix; then
@@ -62,14 +62,14 @@ if has lines; then
   for cm in ${LINES:-c4:inplace c4:compact c4:streams}; do
     IFS=: read c m nd <<< "$cm"
     f=${O}_bench_${c}_${m}${nd:+_nd}.json
-    timeout -k 10 300 python -u bench.py --config $c --mode $m ${nd:+--no-desc} --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --config $c --mode $m ${nd:+--no-desc} --no-cpu-baseline \
       ${BARGS:---steps 20 --warmup 5} > $f 2>> ${O}_bench.err
     line $f "$cm"
   done
 fi
 if has c5x2; then
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 2 --config c5 --steps 2 --warmup 1 --oversubscribe \
+    --master-port 29517 bench.py --full --gpus 2 --config c5 --steps 2 --warmup 1 --oversubscribe \
     > ${O}_c5x2.json 2> ${O}_c5x2.err
   cut -c1-600 ${O}_c5x2.json
 fi
@@ -98,7 +98,7 @@ if has abbuild; then
 fi
 if has walkcmp; then
   for v in "UVHTTP_WS_STREAM_SPEC=1" "UVHTTP_WS_STREAM_SPEC=0" "UVHTTP_WS_STREAM_SPEC=0 UVHTTP_WS_WALK=lane"; do
-    env $v timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --config c4 --mode streams --no-cpu-baseline \
+    env $v timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --config c4 --mode streams --no-cpu-baseline \
       > ${O}_walkcmp.json 2>> ${O}_bench.err
     line ${O}_walkcmp.json "[$v]"
   done

@@ -2,7 +2,7 @@
 // host <-> HBM, 256 MiB, H2D alone, D2H alone, both at once on two streams, a host memcpy (nt
 // stores) into pinned memory alongside the two copies, and the batcher's own shape (reads
 // copied into pinned memory and sent up in 8 MiB pieces while the previous round comes down).
-// One JSON line per repetition.  Built by `make` (tools/bin/pcie_probe); bench.py --e2e runs it
+// One JSON line per repetition.  Built by `make` (tools/bin/pcie_probe); bench.py --full --e2e runs it
 // beside the live-shape batcher so each e2e rate comes with the PCIe ceiling of that box.
 //   pcie_probe [MiB=256] [reps=5]
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-memory pipeline (uvhttp_ws_gpu_pipeline_*) over slot depth x slot size, after the PCIe
-warm-up bench.py --e2e uses: C3 frames (64 KiB), one JSON line per shape.
+warm-up bench.py --full --e2e uses: C3 frames (64 KiB), one JSON line per shape.
 usage: python tools/pipeline_sweep.py [depths, e.g. 4,3] [slot frames, e.g. 1024,2048]"""
 import json
 import os

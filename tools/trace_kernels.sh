@@ -9,7 +9,7 @@ for pair in "$@"; do
   mkdir -p "$OUT"
   cd /tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run \
-    -- python3 "$ROOT/bench.py" --config "$cfg" --mode "$mode" --steps 10 --warmup 2 \
+    -- python3 "$ROOT/bench.py" --full --config "$cfg" --mode "$mode" --steps 10 --warmup 2 \
     --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/err.txt"
   cd "$ROOT"
   echo "== $cfg $mode"
