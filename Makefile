@@ -7,9 +7,13 @@ ARCH ?= gfx950
 BUILD := uvhttp_amd/build
 LIB := uvhttp_amd/lib/libuvhttp_ws_amd.so
 # the same library built with -DUVWS_TEST_HOOKS -DUVWS_EXPERIMENTS (tests and A/B tools only):
-# the batcher's fault-injection hook and the environment switches (UVHTTP_WS_*) the measurements
-# and the variant tests use.  The product library reads no environment.
+# the batcher's fault-injection hook and the environment switches (UVHTTP_WS_*): most force a
+# path the product takes on its own for some input (walk kind, fused / speculative ranges,
+# poll bound, ...), so tests and measurements reach it at a small shape; REC_SCAN, PLAN_WIDE,
+# WALK_FUSE and DESC_EMIT=1 (in place) select measured variants the GPU suite still runs against the
+# oracle.  The product library reads no environment.
 TESTLIB := uvhttp_amd/lib/libuvhttp_ws_amd_testhooks.so
+# reads the switches above (experiment_knobs in ws_gpu.hip and their like in the other sources)
 EXP := -DUVWS_EXPERIMENTS
 
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Iinclude -Wall -Werror \

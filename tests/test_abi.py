@@ -72,18 +72,27 @@ def test_fault_injection_only_in_the_test_build():
     assert b"UVHTTP_WS_BATCHER_FAIL_EVERY" in open(U.TESTHOOKS_LIB_PATH, "rb").read()
 
 
+# switches of decode variants that were measured slower or even and deleted with their code
+REMOVED_KNOBS = ("UVHTTP_WS_STORE_POLICY", "UVHTTP_WS_PLAN_TICKET", "UVHTTP_WS_STREAM_NT",
+                 "UVHTTP_WS_WALK_NT_LOAD", "UVHTTP_WS_COMPACT_RECS", "UVHTTP_WS_FUSED_AUX",
+                 "UVHTTP_WS_FUSED_TILE", "UVHTTP_WS_FIXUP_BLOCKS")
+
+
 def test_product_library_reads_no_environment():
-    """the A/B switches — among them UVHTTP_WS_PLAN_TICKET=0 and
-    UVHTTP_WS_WALK_FUSE=1, whose workgroup orderings rely on in-order dispatch — are compiled
-    only into the experiment build (-DUVWS_EXPERIMENTS); the product library names none of them
-    and imports no getenv at all.  The Python mirror routes an engine created while a switch is
-    set to the experiment build."""
+    """the switches that force a path (UVHTTP_WS_WALK, UVHTTP_WS_FUSED, ...)
+    are compiled only into the experiment build (-DUVWS_EXPERIMENTS); the product library names
+    none of them and imports no getenv at all.  The Python mirror routes an engine created while
+    a switch is set to the experiment build.  Switches of variants that were deleted — among
+    them UVHTTP_WS_PLAN_TICKET=0, whose blockIdx-ordered workgroups relied on in-order dispatch
+    (k_plan and the fused stream walk always take tickets now) — are in neither library."""
     prod = open(U.LIB_PATH, "rb").read()
     exp = open(U.TESTHOOKS_LIB_PATH, "rb").read()
     for k in U.EXPERIMENT_KNOBS:
         assert k.encode() not in prod, k
-    for k in ("UVHTTP_WS_PLAN_TICKET", "UVHTTP_WS_WALK_FUSE", "UVHTTP_WS_COMPACT", "UVHTTP_TLS_CRYPT_GRID"):
+    for k in ("UVHTTP_WS_WALK", "UVHTTP_WS_FUSED", "UVHTTP_WS_COMPACT", "UVHTTP_TLS_CRYPT_GRID"):
         assert k.encode() in exp, k
+    for k in REMOVED_KNOBS:
+        assert k.encode() not in prod and k.encode() not in exp, k
     import subprocess
     syms = subprocess.run(["nm", "-D", "--undefined-only", U.LIB_PATH], capture_output=True,
                           text=True).stdout

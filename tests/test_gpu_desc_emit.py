@@ -156,11 +156,12 @@ def test_c4_full_size(torch, engines):
         _check(torch, engines[:2], w, n, stride, mm=256 << 20)
 
 
-@pytest.fixture(scope="module", params=["2", "1"])
+@pytest.fixture(scope="module", params=["1"])
 def compact_engines(torch, request):
-    """compact decodes with descriptors: k_sum_msgs writing them (info bytes rebuilt from the
-    records, 2, or left by the pass, 1), the speculative pass + k_plan on records + k_spec_fix
-    (UVHTTP_WS_DESC_EMIT=0), k_plan first + the scatter (UVHTTP_WS_SPEC=0)"""
+    """compact decodes with descriptors: k_sum_msgs writing them (records and info bytes left by
+    the pass: every nonzero UVHTTP_WS_DESC_EMIT, the parameter keeps the ids of the time when 2
+    rebuilt the info bytes from the records), the speculative pass + k_plan on records +
+    k_spec_fix (UVHTTP_WS_DESC_EMIT=0), k_plan first + the scatter (UVHTTP_WS_SPEC=0)"""
     e = [_engine({"UVHTTP_WS_DESC_EMIT": request.param}), _engine({"UVHTTP_WS_DESC_EMIT": "0"}),
          _engine({"UVHTTP_WS_SPEC": "0"})]
     e[0].set_stamps(True)

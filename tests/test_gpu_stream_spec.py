@@ -268,3 +268,21 @@ def test_read_tables(torch, engines, cuts):
     # a growth check can fail only where max_frame_size (8 KiB) caps the buffer below what a
     # call holds: then the call goes to the walk
     _run(torch, engines, wire, st, read_end=re)
+
+
+def test_many_connections_after_fewer(torch, engines):
+    """4 096 connections of 8 x 64-byte frames, then 16 384 of them on the same engines (8 MiB of
+    wire, 64 blocks of k_sspec_plan): the speculative scratch has one layout (spec_layout), so
+    the tile claims start after both block-count arrays.  With blk_pre[30..] in use they used to
+    overlie conn_tile[0..]: the prefixes overwrote the first tiles' claims and the 16 384-
+    connection call left the speculative path for the walk (stamps: spec_plan, then walk,
+    walk_scan, stream_desc), as every call from about 7.9 K connections did.  The oracle alone
+    delivers every frame of this input (checked below), so the speculation must hold in both
+    calls."""
+    rng = random.Random(16384)
+    conns = [(_conn_frames(rng, 8, 58, False)[0], b"", 0, 0, 16 << 20, 0) for _ in range(16384)]
+    for n in (4096, 16384):
+        wire, st = _build(conns[:n])
+        out, _, total = _oracle.decode_streams(wire.copy(), st, None, max_frames=9 * n)
+        assert (out["rc"] == 0).all() and (out["n_frames"] == 8).all() and total == 8 * n
+        _run(torch, engines, wire, st, spec_expected=True)

@@ -233,14 +233,12 @@ def test_hooks_library() -> C.CDLL:
 # batchers and pipelines created while one of these is set load the experiment build, so A/B
 # tools and variant tests get the variant they name rather than a silently ignored switch.
 EXPERIMENT_KNOBS = (
-    "UVHTTP_WS_MAX_POLLS", "UVHTTP_WS_SCRATCH_POOL", "UVHTTP_WS_STORE_POLICY", "UVHTTP_WS_PLAN_FPT",
-    "UVHTTP_WS_PLAN_TICKET", "UVHTTP_WS_EPOCH_START", "UVHTTP_WS_BUILD_SMALL", "UVHTTP_WS_FUSED",
-    "UVHTTP_WS_FUSED_MAX", "UVHTTP_WS_PLAN_WIDE", "UVHTTP_WS_REC_SCAN", "UVHTTP_WS_BUILD_FRAMES",
-    "UVHTTP_WS_COMPACT", "UVHTTP_WS_WALK_SINGLE", "UVHTTP_WS_WALK_FUSE", "UVHTTP_WS_STREAM_NT",
-    "UVHTTP_WS_DESC_SCAN", "UVHTTP_WS_WALK_NT_LOAD", "UVHTTP_WS_WALK_REC", "UVHTTP_WS_WALK",
-    "UVHTTP_WS_TIME_CHAIN", "UVHTTP_WS_COMPACT_RECS", "UVHTTP_WS_SPEC", "UVHTTP_WS_SPEC_MAX",
-    "UVHTTP_WS_FUSED_AUX", "UVHTTP_WS_SUMMARY_FAST", "UVHTTP_WS_TILE", "UVHTTP_WS_FIXUP_BLOCKS",
-    "UVHTTP_WS_FUSED_TILE", "UVHTTP_WS_TIMING_FENCE", "UVHTTP_WS_PIPE_IN_FLIGHT",
+    "UVHTTP_WS_MAX_POLLS", "UVHTTP_WS_SCRATCH_POOL", "UVHTTP_WS_PLAN_FPT", "UVHTTP_WS_EPOCH_START",
+    "UVHTTP_WS_BUILD_SMALL", "UVHTTP_WS_FUSED", "UVHTTP_WS_FUSED_MAX", "UVHTTP_WS_PLAN_WIDE",
+    "UVHTTP_WS_REC_SCAN", "UVHTTP_WS_BUILD_FRAMES", "UVHTTP_WS_COMPACT", "UVHTTP_WS_WALK_SINGLE",
+    "UVHTTP_WS_WALK_FUSE", "UVHTTP_WS_DESC_SCAN", "UVHTTP_WS_WALK_REC",
+    "UVHTTP_WS_WALK", "UVHTTP_WS_TIME_CHAIN", "UVHTTP_WS_SPEC", "UVHTTP_WS_SPEC_MAX",
+    "UVHTTP_WS_SUMMARY_FAST", "UVHTTP_WS_TILE", "UVHTTP_WS_TIMING_FENCE", "UVHTTP_WS_PIPE_IN_FLIGHT",
     "UVHTTP_TLS_CRYPT_GRID", "UVHTTP_WS_BATCHER_TRACE", "UVHTTP_WS_BATCHER_FAIL_EVERY",
     "UVHTTP_WS_COPY_SSE2", "UVHTTP_WS_DESC_EMIT", "UVHTTP_WS_STREAM_SPEC")
 

@@ -200,16 +200,7 @@ __device__ ScanElem block_exclusive_scan(ScanElem v, ScanElem* total) {
     __shared__ ScanElem wave_tot[NT / 64];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-#ifdef UVWS_SCAN_BPERMUTE
-    ScanElem inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        ScanElem o = shfl_up_elem(inc, d);
-        if (lane >= d) inc = scan_combine(o, inc);
-    }
-#else
     const ScanElem inc = wave_inclusive_scan(v);
-#endif
     if (lane == 63) wave_tot[wave] = inc;
     __syncthreads();
     ScanElem wave_pre = scan_identity();
@@ -454,7 +445,6 @@ struct BatchArgs {
     uint32_t max_polls;      // look-back wait bound (0: give up at the first wait; tests)
     uvhttp_ws_batch_summary_t* summary;  // batch mode: written by k_finalize
     uint32_t plan_frames;    // frames per k_plan block (kBlock * FPT)
-    uint32_t no_ticket;      // k_plan orders blocks by blockIdx (experiment: UVHTTP_WS_PLAN_TICKET=0)
     uint64_t* stamp;         // device-side kernel stamps (diagnostics), or null
     uint64_t spec_P;         // compact stride batch, speculative pass: the uniform payload length
                              // (frame i's payload at arena offset i * spec_P); 0 = none
@@ -482,10 +472,6 @@ constexpr uint64_t kStampPer = kStampBegin + kStampEnd;
 constexpr uint64_t kStampLow = (1ull << 40) - 1;
 constexpr uint32_t kStampTagPeriod = (1u << 24) - 1;
 constexpr uint64_t kStampWords = (uint64_t)kStampRing * kStampKinds * kStampPer;
-// experiment builds (-DUVWS_PLAN_PHASES, tools/build_variant.sh): k_plan's per-block phase
-// times follow the ring, 8 words per block (uvhttp_ws_gpu_engine_debug_phases)
-constexpr uint64_t kPhaseWords = 8 * 8192;
-constexpr uint64_t kStampAlloc = kStampWords + kPhaseWords;
 
 // a stamp word's call tag: 1 .. 2^24 - 1, never 0 (0 marks an unused word), one more per call
 __host__ __device__ inline uint32_t stamp_tag(uint32_t epoch) { return epoch % kStampTagPeriod + 1u; }
@@ -639,14 +625,11 @@ __device__ inline uint32_t rotr32(uint32_t x, uint32_t s) {
 // come from the two ALIGNED 16-byte vectors around them and a byte funnel shift: an unaligned
 // 16-byte copy compiles to sixteen byte loads on gfx950 (k_plan spent most of its time there).
 // The last 32 bytes of the buffer go bytewise so nothing past `len` is read.
-template <bool NT = false>
 __device__ inline u32x4 load16_at(const uint8_t* base, uint64_t len, uint64_t o) {
     const uint64_t lo = o & ~(uint64_t)15;
     if (len >= 32 && lo <= len - 32) {  // (cannot wrap for o near 2^64)
-        const u32x4 v0 = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + lo))
-                            : *reinterpret_cast<const u32x4*>(base + lo);
-        const u32x4 v1 = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + lo + 16))
-                            : *reinterpret_cast<const u32x4*>(base + lo + 16);
+        const u32x4 v0 = *reinterpret_cast<const u32x4*>(base + lo);
+        const u32x4 v1 = *reinterpret_cast<const u32x4*>(base + lo + 16);
         uint64_t x0 = v0.x | ((uint64_t)v0.y << 32), x1 = v0.z | ((uint64_t)v0.w << 32);
         uint64_t x2 = v1.x | ((uint64_t)v1.y << 32);
         const uint64_t x3 = v1.z | ((uint64_t)v1.w << 32);
@@ -1017,11 +1000,7 @@ __device__ ScanElem lookback_prefix(const Workspace& ws, uint32_t b, const ScanE
     uint32_t polls = 0;              // uniform: every thread counts the same rounds
     bool gave_up = false;
     for (;;) {
-#ifdef UVWS_LOOKBACK_BPERMUTE
-        const int64_t j = end - 1 - t;  // larger t = older block
-#else
         const int64_t j = end - NT + t;  // larger t = newer block (window order = lane order)
-#endif
         ScanElem v = scan_identity();
         bool is_p = j < 0, ready = j < 0;  // lanes before block 0: identity "P"
         for (;;) {
@@ -1043,26 +1022,6 @@ __device__ ScanElem lookback_prefix(const Workspace& ws, uint32_t b, const ScanE
             // back off so waiting blocks do not flood memory while predecessors still parse
             __builtin_amdgcn_s_sleep(8);
         }
-#ifdef UVWS_LOOKBACK_BPERMUTE
-        // nearest published prefix (smallest t with P)
-        if (t == 0) s_kstar = NT;
-        __syncthreads();
-        const uint64_t pm = __ballot(is_p);
-        if (lane == 0 && pm) atomicMin(&s_kstar, wave * 64 + __builtin_ctzll(pm));
-        __syncthreads();
-        const int kstar = s_kstar;
-        if (t > kstar || j < 0) v = scan_identity();
-        v = wave_reduce_newest_first(v);
-        if (lane == 0) s_wave[wave] = v;
-        __syncthreads();
-        if (t == 0) {
-            ScanElem w = scan_identity();
-#pragma unroll
-            for (int k = NT / 64 - 1; k >= 0; --k) w = scan_combine(w, s_wave[k]);
-            run = scan_combine(w, run);
-            s_go = (kstar < NT || gave_up) ? 0 : 1;
-        }
-#else
         // nearest published prefix: the largest t with P; the window from it to the newest
         // block, combined in lane order by the DPP wave scan (lane 63 holds the wave's part)
         if (t == 0) s_kstar = -1;
@@ -1082,7 +1041,6 @@ __device__ ScanElem lookback_prefix(const Workspace& ws, uint32_t b, const ScanE
             run = scan_combine(w, run);
             s_go = (kstar >= 0 || gave_up) ? 0 : 1;
         }
-#endif
         __syncthreads();
         if (!s_go) break;
         end -= NT;
@@ -1124,15 +1082,8 @@ __device__ inline ScanElem rec_pass1(const BatchArgs& a, uint32_t i0, uint32_t n
     return tagg;
 }
 
-// one descriptor store (UVWS_DESC_NT, experiment: two streaming 16-byte stores)
 __device__ inline void store_desc(uvhttp_ws_frame_desc_t* desc, uint32_t i, const uvhttp_ws_frame_desc_t& d) {
-#ifdef UVWS_DESC_NT
-    const u32x4* w = reinterpret_cast<const u32x4*>(&d);
-    __builtin_nontemporal_store(w[0], reinterpret_cast<u32x4*>(desc + i));
-    __builtin_nontemporal_store(w[1], reinterpret_cast<u32x4*>(desc + i) + 1);
-#else
     desc[i] = d;
-#endif
 }
 
 // pass 2: the state machine in frame order from the lane's exclusive prefix `run`; each
@@ -1172,39 +1123,16 @@ __global__ __launch_bounds__(NT) void k_plan(BatchArgs a, uvhttp_ws_frame_desc_t
     StampScope stamp_(a.stamp, a.epoch, UVHTTP_WS_STAMP_PLAN);
     __shared__ uint32_t s_ticket;
     if (threadIdx.x == 0) {
-        uint32_t t = blockIdx.x;
-        if (!a.no_ticket) {
-            t = __hip_atomic_fetch_add(&ws.counters[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t + 1 == gridDim.x)
-                __hip_atomic_store(&ws.counters[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        const uint32_t t =
+            __hip_atomic_fetch_add(&ws.counters[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t + 1 == gridDim.x)
+            __hip_atomic_store(&ws.counters[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_ticket = t;
     }
     __syncthreads();
     const uint32_t b = s_ticket;
     const uint32_t n = nframes(a);
     const uint32_t i0 = (b * NT + threadIdx.x) * FPT;
-#ifdef UVWS_PLAN_PHASES
-    // per block: [0] start (after the ticket) [1] thread 0's pass 1 done [2] block scan done
-    // [3] look-back done [4] thread 0's pass 2 done [5] latest wave end, [6] blockIdx, [7] CU id
-    unsigned long long* ph = a.stamp && b < 8192 ? reinterpret_cast<unsigned long long*>(a.stamp + kStampWords + 8ull * b) : nullptr;
-    auto phase = [&](int k) {
-        if (ph && threadIdx.x == 0) ph[k] = (unsigned long long)wall_clock64();
-    };
-    phase(0);
-    if (ph && threadIdx.x == 0) {
-        ph[6] = blockIdx.x;
-        ph[7] = __smid();
-    }
-    struct PhaseEnd {
-        unsigned long long* p;
-        __device__ ~PhaseEnd() {
-            if (p && (threadIdx.x & 63) == 0) atomicMax(p + 5, (unsigned long long)wall_clock64());
-        }
-    } phase_end_{ph};
-#else
-    auto phase = [](int) {};
-#endif
     if constexpr (REC) {
         // records path: the lane's 8-byte records stay in registers across the scan (the
         // 32-byte descriptors built from them took 128 registers and spilled at 16 frames per
@@ -1224,12 +1152,9 @@ __global__ __launch_bounds__(NT) void k_plan(BatchArgs a, uvhttp_ws_frame_desc_t
                 tagg = scan_combine(tagg, elem_of_parsed(d, i, i == 0));
             }
         }
-        phase(1);
         ScanElem agg;
         const ScanElem local = block_exclusive_scan<NT>(tagg, &agg);
-        phase(2);
         ScanElem run = scan_combine(lookback_prefix<NT>(ws, b, agg, a.epoch, a.max_polls), local);
-        phase(3);
 #pragma unroll
         for (int k = 0; k < FPT; ++k) {
             const uint32_t i = i0 + k;
@@ -1243,7 +1168,6 @@ __global__ __launch_bounds__(NT) void k_plan(BatchArgs a, uvhttp_ws_frame_desc_t
                 run = scan_combine(run, e);
             }
         }
-        phase(4);
         return;
     }
     if (FPT == 1) {
@@ -1259,17 +1183,13 @@ __global__ __launch_bounds__(NT) void k_plan(BatchArgs a, uvhttp_ws_frame_desc_t
                 elem = parse_one(a, i0, g, d);
             }
         }
-        phase(1);
         ScanElem agg;
         const ScanElem local = block_exclusive_scan<NT>(elem, &agg);
-        phase(2);
         const ScanElem pre = lookback_prefix<NT>(ws, b, agg, a.epoch, a.max_polls);
-        phase(3);
         if (i0 < n) {
             resolve_one(a, msgs, ws, i0, n, g, scan_combine(pre, local), d);
             desc[i0] = d;
         }
-        phase(4);
         return;
     }
     // pass 1: all header loads of the lane's frames in flight together, then parse into
@@ -1301,14 +1221,10 @@ __global__ __launch_bounds__(NT) void k_plan(BatchArgs a, uvhttp_ws_frame_desc_t
             if (i < n) tagg = scan_combine(tagg, parse_hdr(a, i, seg_info(a, i, n), o[k], hv[k], dv[k]));
         }
     }
-    phase(1);
     ScanElem agg;
     const ScanElem local = block_exclusive_scan<NT>(tagg, &agg);
-    phase(2);
     ScanElem run = scan_combine(lookback_prefix<NT>(ws, b, agg, a.epoch, a.max_polls), local);
-    phase(3);
     plan_pass2<FPT>(a, desc, msgs, ws, i0, n, run, dv);
-    phase(4);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1523,9 +1439,10 @@ __device__ inline bool any_bits(const u32x4& m) { return (m.x | m.y | m.z | m.w)
 // wire belongs to exactly one tile, so whole-vector stores never race: bytes outside any
 // delivered payload are XORed with 0 and vectors with no payload byte are not stored.
 // ------------------------------------------------------------------------------------
-// store-path cache policy of the payload pass: 0 = global_store nt; 18 = buffer_store with
-// sc1|nt (write-through, not kept in L2), measured 1.7 % faster for the 64x1 shape
+// store-path cache policy of the payload passes: buffer_store with sc1|nt (write-through, not
+// kept in L2), measured 1.7 % faster than global_store nt for the 64x1 shape
 // (tools/stream_probe.hip, profiles/r01_stream_probe_policy.txt)
+constexpr int kStoreAux = 18;
 // the in-place payload kernel's tile shape by average wire bytes per frame (tools/ab_lib.py
 // UVHTTP_WS_TILE sweeps, profiles/r04_tile_sizes_ab.txt): since the scalar-descriptor path takes
 // up to kFastFrames frames per tile, small tiles win from 2.5 KiB frames up — 2 KiB tiles
@@ -1537,11 +1454,8 @@ __host__ inline void inplace_tile_shape(uint64_t avg, int& blk, int& vpt) {
     else blk = 256, vpt = avg >= 2048 ? 2 : 4;
 }
 
-#ifndef UVWS_FAST_FRAMES
-#define UVWS_FAST_FRAMES 8
-#endif
-constexpr uint32_t kFastFrames = UVWS_FAST_FRAMES;  // scalar-descriptor path up to this many frames
-template <int BLOCK, int VPT, int STORE_AUX>
+constexpr uint32_t kFastFrames = 8;  // scalar-descriptor path up to this many frames
+template <int BLOCK, int VPT>
 __device__ __forceinline__ void unmask_tile(BatchArgs a,
                                             const uvhttp_ws_frame_desc_t* __restrict__ desc,
                                             const Workspace& ws, uint64_t tile_base,
@@ -1661,26 +1575,18 @@ __device__ __forceinline__ void unmask_tile(BatchArgs a,
         }
     }
 
-    if (STORE_AUX == 0) {
+    // buffer resource over this tile (wave-uniform: built from kernel args + blockIdx)
+    const uint64_t room = vend > t0 ? vend - t0 : 0;
+    const uint32_t nrec = (uint32_t)(room < kT ? room : kT);
+    __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(a.wire + t0, 0, (int)nrec, 0x00020000);
 #pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            if (any_bits(m[v]) && va[v] + 16 <= vend)
-                __builtin_nontemporal_store(data[v] ^ m[v], reinterpret_cast<u32x4*>(a.wire + va[v]));
-        }
-    } else {
-        // buffer resource over this tile (wave-uniform: built from kernel args + blockIdx)
-        const uint64_t room = vend > t0 ? vend - t0 : 0;
-        const uint32_t nrec = (uint32_t)(room < kT ? room : kT);
-        __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(a.wire + t0, 0, (int)nrec, 0x00020000);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            if (any_bits(m[v]) && va[v] + 16 <= vend) {
-                const u32x4 x = data[v] ^ m[v];
-                __builtin_amdgcn_raw_buffer_store_b128(
-                    __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, x), rs,
-                    (uint32_t)(va[v] - t0), 0, STORE_AUX);
-            }
+    for (int v = 0; v < VPT; ++v) {
+        if (any_bits(m[v]) && va[v] + 16 <= vend) {
+            const u32x4 x = data[v] ^ m[v];
+            __builtin_amdgcn_raw_buffer_store_b128(
+                __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, x), rs,
+                (uint32_t)(va[v] - t0), 0, kStoreAux);
         }
     }
     // the single vector that straddles the end of the wire: byte stores
@@ -1714,13 +1620,13 @@ __device__ inline void stream_fix(const BatchArgs& a, const Workspace& ws) {
     }
 }
 
-template <int BLOCK, int VPT, int STORE_AUX = 0>
+template <int BLOCK, int VPT>
 __global__ __launch_bounds__(BLOCK) void k_unmask_inplace(
     BatchArgs a, const uvhttp_ws_frame_desc_t* __restrict__ desc, Workspace ws,
     uint64_t tile_base) {
     StampScope stamp_(a.stamp, a.epoch, UVHTTP_WS_STAMP_PAYLOAD, false, tile_base);
     uint32_t n, nb;
-    unmask_tile<BLOCK, VPT, STORE_AUX>(a, desc, ws, tile_base, n, nb, stamp_);  // resolves the epoch
+    unmask_tile<BLOCK, VPT>(a, desc, ws, tile_base, n, nb, stamp_);  // resolves the epoch
     // batch in-place decode: the first ceil(n / BLOCK) workgroups then do k_finalize's work
     // (statuses after the first failure become SKIPPED — frames no tile reads — and the
     // summary); the launch covers max(tiles, those blocks).  After the tile, so the tile's
@@ -1759,9 +1665,6 @@ constexpr uint64_t kFusedMinStride = 64;
 // 16 KiB fused tiles made the sweep favour fusing up to 8 KiB (r03p35_fused_tiles.txt), but
 // the C2 bench itself (4 KiB frames) lost 5 % fused: 2217-2255 vs 2357-2367 GiB/s (r03p36)
 constexpr uint64_t kFusedMaxAvg = 2560;
-// k_unmask_stride's third role (AUX == kSpecCompact): the speculative pass of a compact stride
-// batch (run_decode)
-constexpr int kSpecCompact = 100;
 
 // 16 bytes at byte offset r of an LDS-staged tile, from the two aligned vectors around it
 __device__ inline u32x4 lds_window(const u32x4* tile, uint32_t r) {
@@ -1855,7 +1758,9 @@ __device__ inline void add_mask_rel(u32x4& m, int32_t r, int32_t ps, int32_t pe,
 // what the payload pass leaves per frame: a 16-byte record (k_plan on records), an info byte
 // (the summary-only scan), or both (records for k_desc_emit, info bytes for its scan)
 constexpr int kLeaveRec = 0, kLeaveInfo = 1, kLeaveBoth = 2;
-template <int BLOCK, int VPT, int AUX = 18, int SUM = kLeaveRec>
+// SPEC: the kernel's other role, the speculative pass of a compact stride batch (run_decode,
+// DESIGN.md §4)
+template <int BLOCK, int VPT, bool SPEC = false, int SUM = kLeaveRec>
 __global__ __launch_bounds__(BLOCK) void k_unmask_stride(BatchArgs a, Workspace ws, uint64_t tile_base) {
     StampScope stamp_(a.stamp, a.epoch, UVHTTP_WS_STAMP_PAYLOAD, false, tile_base);
     constexpr uint64_t kT = (uint64_t)BLOCK * VPT * 16;
@@ -1928,16 +1833,14 @@ __global__ __launch_bounds__(BLOCK) void k_unmask_stride(BatchArgs a, Workspace 
         const bool ok = d.status == UVHTTP_WS_FRAME_OK;
         // speculative compact pass: the frame is uniform (a locally valid data frame with the
         // batch's uniform payload length and header + key bytes), so it goes to f * spec_P
-        const bool uniform = AUX == kSpecCompact && ok && d.opcode <= 2 && d.payload_len == a.spec_P &&
+        const bool uniform = SPEC && ok && d.opcode <= 2 && d.payload_len == a.spec_P &&
                              d.header_size + ((d.flags & UVHTTP_WS_FLAG_MASK) ? 4u : 0u) == S - a.spec_P;
         s_fr[j] = int4{rel_clamp(d.payload_off, t0, kT, true),
                        rel_clamp(d.payload_off + (ok ? d.payload_len : 0), t0, kT, false),
                        (int32_t)d.masking_key, uniform ? 1 : 0};
     }
-    // AUX < 0: the records-only pass of a compact stride decode (the wire stays masked)
-    if constexpr (AUX < 0) return;
     __syncthreads();
-    if constexpr (AUX == kSpecCompact) {
+    if constexpr (SPEC) {
         // The speculative compact pass: the tile's payload bytes of uniform frames go to arena
         // offset f * P + q (P = spec_P, q = byte within the payload) — where the compact decode
         // puts them when every frame before f is uniform and delivered, which k_plan checks
@@ -1980,7 +1883,7 @@ __global__ __launch_bounds__(BLOCK) void k_unmask_stride(BatchArgs a, Workspace 
                     const u32x4 outv = lds_window(s_tile, rw) ^ u32x4{rk, rk, rk, rk};
                     __builtin_amdgcn_raw_buffer_store_b128(
                         __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, outv), rs,
-                        (uint32_t)(ov - base), 0, 18);
+                        (uint32_t)(ov - base), 0, kStoreAux);
                     continue;
                 }
             }
@@ -2013,7 +1916,7 @@ __global__ __launch_bounds__(BLOCK) void k_unmask_stride(BatchArgs a, Workspace 
                                     (uint32_t)(acc >> 96)};
                 __builtin_amdgcn_raw_buffer_store_b128(
                     __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, outv), rs,
-                    (uint32_t)(ov - base), 0, 18);
+                    (uint32_t)(ov - base), 0, kStoreAux);
             } else if (valid) {
                 for (uint32_t bq = 0; bq < 16; ++bq)
                     if (valid & (1u << bq)) a.arena[ov + bq] = (uint8_t)(acc >> (8 * bq));
@@ -2058,7 +1961,7 @@ __global__ __launch_bounds__(BLOCK) void k_unmask_stride(BatchArgs a, Workspace 
             const u32x4 x = data[v] ^ m[v];
             __builtin_amdgcn_raw_buffer_store_b128(
                 __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, x), rs,
-                (uint32_t)(va[v] - t0), 0, AUX < 0 ? 0 : AUX);
+                (uint32_t)(va[v] - t0), 0, kStoreAux);
         }
     }
     if (full_end != vend && full_end >= t0 && full_end < t0 + kT) {
@@ -2092,6 +1995,8 @@ __device__ inline void remask_range(uint8_t* wire, uint64_t ps, uint64_t pe, uin
         *p = *p ^ u32x4{rk, rk, rk, rk};
     }
 }
+
+constexpr uint32_t kFixupBlocks = 1024;  // k_fixup's grid cap (its blocks stride over the frames)
 
 // After the fused path's k_plan: statuses after the first failure become SKIPPED, block 0
 // writes the summary, and every frame the payload pass unmasked from the first failure on is
@@ -2483,10 +2388,10 @@ __device__ inline void parts_fin_start(const TilePart* parts, uint32_t hi, uint3
 // count, the latest start and whether the last delivered frame left its message open.
 // (One launch after the scan; a single-block tail leaving ordered prefixes + this kernel took
 // 6.4 + 2.0 us and a boundary on C4, every block combining full parts in order 9.2 us.)
-// DESC (compact decode with descriptors, the payload pass leaving 16-byte records: FROM_REC):
-// every block also writes its 1024 frames' descriptors as k_desc_emit does, data frames at their
+// DESC (compact decode with descriptors, the payload pass leaving records in a.recs and info
+// bytes in ws.info): every block also writes its 1024 frames' descriptors as k_desc_emit does, data frames at their
 // arena offset f * P; a call whose speculation failed has them rewritten by the fall-back.
-template <bool FROM_REC = false, bool DESC = false>
+template <bool DESC = false>
 __global__ __launch_bounds__(kBlock) void k_sum_msgs(BatchArgs a, Workspace ws, uint32_t n_parts,
                                                      uvhttp_ws_message_desc_t* msgs,
                                                      uvhttp_ws_frame_desc_t* desc = nullptr) {
@@ -2501,24 +2406,11 @@ __global__ __launch_bounds__(kBlock) void k_sum_msgs(BatchArgs a, Workspace ws, 
     const uint32_t nb = first_bad_of(a, ws, n);
     const uint32_t sb = tag_get(*ws.spec_bad, a.epoch, n);
     const uint32_t end = nb < n - 1 ? nb : n - 1;  // frames [0, end) here, the last one is block 0's
-    // (DESC without FROM_REC: records in a.recs, the payload pass's info bytes in ws.info)
-    const uint8_t* info_b = (DESC && !FROM_REC) ? ws.info : reinterpret_cast<const uint8_t*>(a.recs);
-    auto info_at = [&](uint32_t f) -> uint32_t {
-        if constexpr (FROM_REC) return info_of_rec(a, a.recs[f], S, f);
-        else return info_b[f];
-    };
+    // (DESC: records in a.recs, the payload pass's info bytes in ws.info)
+    const uint8_t* info_b = DESC ? ws.info : reinterpret_cast<const uint8_t*>(a.recs);
+    auto info_at = [&](uint32_t f) -> uint32_t { return info_b[f]; };
     const uint32_t F0 = (blockIdx.x * kBlock + threadIdx.x) * kScanFpt;
-    uint32_t w = 0u;
-    if constexpr (FROM_REC) {
-        FrameRec8 r4[kScanFpt];
-#pragma unroll
-        for (uint32_t k = 0; k < kScanFpt; ++k) r4[k] = a.recs[F0 + k < n ? F0 + k : n - 1];
-#pragma unroll
-        for (uint32_t k = 0; k < kScanFpt; ++k)
-            if (F0 + k < n) w |= info_of_rec(a, r4[k], S, F0 + k) << (8 * k);
-    } else {
-        w = F0 < n ? *reinterpret_cast<const uint32_t*>(info_b + F0) : 0u;
-    }
+    const uint32_t w = F0 < n ? *reinterpret_cast<const uint32_t*>(info_b + F0) : 0u;
     constexpr uint32_t kPartFrames = kBlock * kScanFpt;
     // block 0: the parts of every frame before `end` (a part stops at its first failure)
     const uint32_t hi = head ? (end / kPartFrames + 1 < n_parts ? end / kPartFrames + 1 : n_parts) : blockIdx.x;
@@ -2581,7 +2473,7 @@ __global__ __launch_bounds__(kBlock) void k_sum_msgs(BatchArgs a, Workspace ws, 
 #pragma unroll
         for (uint32_t k = 0; k < kScanFpt; ++k) {
             const uint32_t f = B0 + k * kBlock + threadIdx.x;
-            x[k] = f < n ? (FROM_REC ? info_of_rec(r[k], S, f) : (uint32_t)info_b[f]) : 0u;
+            x[k] = f < n ? (uint32_t)info_b[f] : 0u;
         }
         uint64_t v = 0;
 #pragma unroll
@@ -2979,31 +2871,6 @@ __global__ __launch_bounds__(BLOCK) void k_gather_compact(
 // ------------------------------------------------------------------------------------
 // bytes [0, n) of v (little-endian) to p, n <= 16
 __device__ inline void store_lo_bytes(uint8_t* p, unsigned __int128 v, int n) {
-#ifdef UVWS_SCATTER_NT
-    // (experiment: streaming stores, so no dirty arena lines are left behind in the caches)
-    if (n == 16) {
-        const u32x4 x = {(uint32_t)v, (uint32_t)(v >> 32), (uint32_t)(v >> 64), (uint32_t)(v >> 96)};
-        __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(p));
-        return;
-    }
-    if (n & 8) {
-        __builtin_nontemporal_store((uint64_t)v, reinterpret_cast<uint64_t*>(p));
-        p += 8;
-        v >>= 64;
-    }
-    if (n & 4) {
-        __builtin_nontemporal_store((uint32_t)v, reinterpret_cast<uint32_t*>(p));
-        p += 4;
-        v >>= 32;
-    }
-    if (n & 2) {
-        __builtin_nontemporal_store((uint16_t)v, reinterpret_cast<uint16_t*>(p));
-        p += 2;
-        v >>= 16;
-    }
-    if (n & 1) __builtin_nontemporal_store((uint8_t)v, p);
-    return;
-#endif
     if (n == 16) {
         __builtin_memcpy(p, &v, 16);
         return;
@@ -3241,11 +3108,8 @@ struct WalkArgs {
     uint64_t* stamp;           // device-side kernel stamps (diagnostics), or null
     uint32_t cas_claims;       // the engine has captured calls (tag_claim)
     uint32_t max_polls;        // k_swalk_fused look-back wait bound (BatchArgs::max_polls)
-    uint32_t no_ticket;        // k_swalk_fused: blocks in blockIdx order (UVHTTP_WS_PLAN_TICKET=0)
     uint64_t* first_bad;       // Workspace::first_bad (k_swalk_fused: a look-back give-up)
-    uint32_t nt_stores;        // UVHTTP_WS_STREAM_NT=1: frame records and descriptors as streaming stores
     uint32_t desc_scan;        // k_stream_desc finds first frames itself (no k_swalk_scan)
-    uint32_t nt_loads;         // UVHTTP_WS_WALK_NT_LOAD=1: the wave walk's header loads non-temporal (A/B)
     uint32_t spec;             // the speculative decode ran first: walk only if it gave way (spec_slow)
 };
 
@@ -3632,16 +3496,8 @@ __device__ inline uvhttp_ws_stream_result_t walk_wave(const WalkArgs& w, uint32_
         if (MODE == 0 || !on) return;
         const uint64_t f = first + idx;
         if (MODE >= 2) {
-            if (w.nt_stores) {
-                __builtin_nontemporal_store((uint32_t)pos, &w.sc.walk_tmp[f]);
-                if (w.sc.walk_rec) {
-                    __builtin_nontemporal_store(rec.x, &w.sc.walk_rec[f].x);
-                    __builtin_nontemporal_store(rec.y, &w.sc.walk_rec[f].y);
-                }
-            } else {
-                w.sc.walk_tmp[f] = (uint32_t)pos;
-                if (w.sc.walk_rec) w.sc.walk_rec[f] = rec;
-            }
+            w.sc.walk_tmp[f] = (uint32_t)pos;
+            if (w.sc.walk_rec) w.sc.walk_rec[f] = rec;
         } else if (f < w.max_frames) {
             w.sc.frame_off[f] = st.begin + pos;
         }
@@ -3710,10 +3566,7 @@ __device__ inline uvhttp_ws_stream_result_t walk_wave(const WalkArgs& w, uint32_
             // a header's 16 bytes (issued apart from the decode, so several are in flight), then
             // its fields and the frame's record for k_stream_desc: key and header bytes, kNoRec
             // for a 64-bit length
-            auto fetch = [&](uint64_t p) {
-                return w.nt_loads ? load16_at<true>(w.wire, w.wire_len, st.begin + p)
-                                  : load16_at(w.wire, w.wire_len, st.begin + p);
-            };
+            auto fetch = [&](uint64_t p) { return load16_at(w.wire, w.wire_len, st.begin + p); };
             auto decode16 = [&](const u32x4& v, uint32_t& b0, uint32_t& wl, uint64_t& plen, bool& bad,
                                 uint2& rec) {
                 const uint32_t x[4] = {v.x, v.y, v.z, v.w};
@@ -3768,14 +3621,10 @@ __device__ inline uvhttp_ws_stream_result_t walk_wave(const WalkArgs& w, uint32_
                 uint2 recl[kG];  // lane l of group g: the record of frame 1 + l + 64 g
 #pragma unroll
                 for (uint32_t g = 0; g < kG; ++g) recl[g] = uint2{0u, kNoRec};
-#ifdef UVWS_WALK_SPEC_FIRST_OFF
-                const bool spec = wl0 == wlp;
-#else
                 // (the first step speculates on frame 0's own length: one dependent header
                 // round trip fewer per connection; a connection of unequal frames wastes one
                 // step's loads)
                 const bool spec = wl0 == wlp || wlp == 0;
-#endif
                 if (kind != 3 && spec) {
                     // speculation: frames 1 .. kRun all have frame 0's length, so the frame after
                     // the run — the next step's frame 0 — was always read, even after a full run
@@ -4124,13 +3973,7 @@ __device__ inline void stream_desc_wave(const WalkArgs& w, uint32_t s, const uvh
             const uint32_t before = msg + (uint32_t)__builtin_popcountll(fm & ((1ull << lane) - 1));
             if (act) {
                 if (d.status == UVHTTP_WS_FRAME_OK && d.opcode <= 2) d.message = before;
-                if (w.nt_stores) {
-                    const u32x4* dw = reinterpret_cast<const u32x4*>(&d);
-                    __builtin_nontemporal_store(dw[0], reinterpret_cast<u32x4*>(w.desc + r.first_frame + k));
-                    __builtin_nontemporal_store(dw[1], reinterpret_cast<u32x4*>(w.desc + r.first_frame + k) + 1);
-                } else {
-                    w.desc[r.first_frame + k] = d;
-                }
+                w.desc[r.first_frame + k] = d;
             }
             msg += (uint32_t)__builtin_popcountll(fm);
         }
@@ -4883,7 +4726,7 @@ __global__ __launch_bounds__(kBlock) void k_sspec_fallback(SpecArgs sa, BatchArg
             __syncthreads();
         }
         uint32_t n, nb;
-        unmask_tile<kBlock, 4, 18>(a, desc, ws, t - blockIdx.x, n, nb, ss);
+        unmask_tile<kBlock, 4>(a, desc, ws, t - blockIdx.x, n, nb, ss);
     }
 }
 
@@ -5009,11 +4852,8 @@ __global__ __launch_bounds__(kBlock) void k_swalk_fused(WalkArgs w) {
     __shared__ __attribute__((aligned(16))) uint8_t ring[kBlock / 64][kRingBytes];
     __shared__ uint32_t s_ticket;
     if (threadIdx.x == 0) {
-        uint32_t t = blockIdx.x;
-        if (!w.no_ticket) {
-            t = __hip_atomic_fetch_add(&w.sc.ctr[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t + 1 == gridDim.x) __hip_atomic_store(&w.sc.ctr[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        const uint32_t t = __hip_atomic_fetch_add(&w.sc.ctr[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t + 1 == gridDim.x) __hip_atomic_store(&w.sc.ctr[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_ticket = t;
     }
     __syncthreads();
@@ -5399,18 +5239,11 @@ __global__ __launch_bounds__(BLOCK) void kb_emit(BuildArgs b, uint64_t tile_base
 // unaligned 16-byte source load — no per-tile map records and no per-vector frame search
 // over the whole tile.
 constexpr uint32_t kEmitF = 256;         // frames per workgroup at most (one per thread; FMAX)
-#ifndef UVWS_EMIT_WIN
-#define UVWS_EMIT_WIN 20480
-#endif
-constexpr uint32_t kEmitWin = UVWS_EMIT_WIN;  // LDS window bytes (64 frames of <= 300 bytes: one window)
+constexpr uint32_t kEmitWin = 20480;     // LDS window bytes (64 frames of <= 300 bytes: one window)
 constexpr uint32_t kEmitItems = 1280;    // item -> frame table entries (one-window workgroups; 5 per thread)
 
 template <int BLOCK, int FMAX>
-__global__ __launch_bounds__(BLOCK)
-#ifdef UVWS_EMIT_WPE
-__attribute__((amdgpu_waves_per_eu(UVWS_EMIT_WPE)))
-#endif
-void kb_emit_frames(BuildArgs b) {
+__global__ __launch_bounds__(BLOCK) void kb_emit_frames(BuildArgs b) {
     __shared__ u32x4 s_win[kEmitWin / 16];
     __shared__ uint64_t s_ps[FMAX], s_fe[FMAX], s_sp[FMAX], s_st[FMAX];
     __shared__ uint32_t s_key[FMAX];
@@ -5754,14 +5587,12 @@ struct uvhttp_ws_gpu_engine {
     int timing;                // 0: off; k >= 1: HIP events around every k-th call's payload kernel
     uint64_t timing_calls;     // calls seen while timing (the sampling counter)
     int tile_block, tile_vpt;  // payload kernel shape, 0 = automatic
-    int store_aux;             // payload store cache policy (0 = nt global store, 18 = sc1|nt)
     uint32_t epoch;            // tag of the latest decode call, 1 .. kMaxEpoch
     int plan_fpt;              // k_plan frames per lane, 0 = automatic
     int fused_off;             // UVHTTP_WS_FUSED=0: stride batches take the k_plan-first path
     uint64_t fused_max_avg;    // fused only up to this many wire bytes per frame (UVHTTP_WS_FUSED_MAX)
     int rec_lookback;          // fused path: records scanned by k_plan (1) or reduce-then-scan (0)
     int plan_wide;             // records: k_plan with 1024-thread blocks (UVHTTP_WS_PLAN_WIDE=1; A/B)
-    uint32_t plan_no_ticket;   // UVHTTP_WS_PLAN_TICKET=0: blockIdx order instead of tickets
     int walk_mode;             // stream frame discovery: 0 automatic, 1 lane, 2 wave
     void* ss_mem;              // stream-decode scratch
     uint32_t ss_frames, ss_reads;
@@ -5773,18 +5604,12 @@ struct uvhttp_ws_gpu_engine {
     int wr_rec_on;             // UVHTTP_WS_WALK_REC=0: k_stream_desc gathers every header (A/B)
     int walk_single_off;       // UVHTTP_WS_WALK_SINGLE=0: always walk twice (tests, A/B)
     int walk_fuse;             // UVHTTP_WS_WALK_FUSE=1: k_swalk_fused for the single-pass wave walk
-    int stream_nt;             // UVHTTP_WS_STREAM_NT=1: streaming stores in the walk and k_stream_desc (A/B)
     int desc_scan_off;         // UVHTTP_WS_DESC_SCAN=0: k_swalk_scan before k_stream_desc always (A/B)
-    int walk_nt_load;          // UVHTTP_WS_WALK_NT_LOAD=1: non-temporal header loads in the wave walk (A/B)
     int stream_spec;           // stream calls try the speculative decode first (k_sspec_*;
                                // UVHTTP_WS_STREAM_SPEC=0: the walk always)
     void* sp_mem;              // its scratch: SpecConn per connection, block counts, tile claims
     uint32_t sp_streams;
     uint64_t sp_tiles;
-    int fused_block, fused_vpt;  // UVHTTP_WS_FUSED_TILE=BxV: the fused payload pass's tile (A/B)
-    uint32_t fixup_blocks;     // k_fixup grid cap (UVHTTP_WS_FIXUP_BLOCKS, A/B)
-    int fused_aux;             // fused payload stores' cache-policy bits (UVHTTP_WS_FUSED_AUX, A/B)
-    int compact_recs;          // compact stride batches: records pass + k_plan on records
     int spec_on;               // compact stride batches: the speculative pass (UVHTTP_WS_SPEC=0: off)
     uint64_t spec_max_avg;     // ... up to this many wire bytes per frame (UVHTTP_WS_SPEC_MAX)
     int time_chain;            // UVHTTP_WS_TIME_CHAIN=1: stream decode timing brackets the whole
@@ -5807,7 +5632,9 @@ struct uvhttp_ws_gpu_engine {
     hipStream_t last_stream;   // stream of the previous call (calls are serialised on it)
     int have_last;
     int pool_ok;               // the device has the stream-ordered allocator (scratch_grow)
-    int desc_emit;             // stride batches with descriptors: k_desc_emit (not k_plan on records)
+    int desc_emit;             // stride batches with descriptors under sum_ok(): k_desc_emit / k_sum_msgs
+                               // write them (0: k_plan on the records; in place 1: info bytes left by the
+                               // payload pass, A/B; 2: rebuilt from the records, the product)
     hipEvent_t order_ev;       // orders a call on a new stream after the previous stream's work
     hipEvent_t ev[2 * 1024];
     int ev_created;
@@ -5845,16 +5672,13 @@ uint64_t uvhttp_ws_gen_frame_stride(uint64_t payload_len) {
 #ifdef UVWS_EXPERIMENTS
 // Experiment / test builds only (libuvhttp_ws_amd_testhooks.so, -DUVWS_EXPERIMENTS): the A/B
 // switches the measurements in DESIGN.md and profiles/ were taken with, and the test hooks
-// (look-back give-up, epoch wrap).  The product library reads no environment: two of these
-// (UVHTTP_WS_PLAN_TICKET=0, UVHTTP_WS_WALK_FUSE=1) order workgroups by blockIdx and rely on
-// in-order dispatch, which the product must not.  Every
-// variant reachable here gives the product's results (tests/ run them against the oracle).
+// (look-back give-up, epoch wrap).  The product library reads no environment (VERDICT r05
+// item 9).  Every variant reachable here takes block tickets where it waits on other blocks
+// and gives the product's results (tests/ run them against the oracle).
 static void experiment_knobs(uvhttp_ws_gpu_engine_t* e) {
     if (const char* mp = getenv("UVHTTP_WS_MAX_POLLS")) e->max_polls = (uint32_t)strtoul(mp, nullptr, 0);
     if (const char* po = getenv("UVHTTP_WS_SCRATCH_POOL")) e->pool_ok &= atoi(po) != 0;
-    if (const char* sp = getenv("UVHTTP_WS_STORE_POLICY")) e->store_aux = atoi(sp) == 18 ? 18 : 0;
     if (const char* fp = getenv("UVHTTP_WS_PLAN_FPT")) e->plan_fpt = atoi(fp);
-    if (const char* pt = getenv("UVHTTP_WS_PLAN_TICKET")) e->plan_no_ticket = atoi(pt) == 0;
     // start near the end of the epoch space to exercise the wrap-around clear
     if (const char* ep = getenv("UVHTTP_WS_EPOCH_START")) {
         const unsigned long v = strtoul(ep, nullptr, 0);
@@ -5863,39 +5687,26 @@ static void experiment_knobs(uvhttp_ws_gpu_engine_t* e) {
     if (const char* bs = getenv("UVHTTP_WS_BUILD_SMALL")) e->build_small = atoi(bs);
     if (const char* fu = getenv("UVHTTP_WS_FUSED")) e->fused_off = atoi(fu) == 0;
     if (const char* fm = getenv("UVHTTP_WS_FUSED_MAX")) e->fused_max_avg = strtoull(fm, nullptr, 10);
-    if (const char* pw = getenv("UVHTTP_WS_PLAN_WIDE")) e->plan_wide = atoi(pw);
+    if (const char* pw = getenv("UVHTTP_WS_PLAN_WIDE")) e->plan_wide = atoi(pw) != 0;
     if (const char* rs = getenv("UVHTTP_WS_REC_SCAN")) e->rec_lookback = strcmp(rs, "3pass") != 0;
     if (const char* bf = getenv("UVHTTP_WS_BUILD_FRAMES")) e->build_frames_max = strtoull(bf, nullptr, 10);
     if (const char* cm = getenv("UVHTTP_WS_COMPACT"))
         e->compact_mode = strcmp(cm, "gather") == 0 ? 1 : strcmp(cm, "scatter") == 0 ? 2 : 0;
     if (const char* ws = getenv("UVHTTP_WS_WALK_SINGLE")) e->walk_single_off = atoi(ws) == 0;
     if (const char* wf = getenv("UVHTTP_WS_WALK_FUSE")) e->walk_fuse = atoi(wf) != 0;
-    if (const char* sn = getenv("UVHTTP_WS_STREAM_NT")) e->stream_nt = atoi(sn) != 0;
     if (const char* ds = getenv("UVHTTP_WS_DESC_SCAN")) e->desc_scan_off = atoi(ds) == 0;
-    if (const char* wn = getenv("UVHTTP_WS_WALK_NT_LOAD")) e->walk_nt_load = atoi(wn) != 0;
     if (const char* sq = getenv("UVHTTP_WS_STREAM_SPEC")) e->stream_spec = atoi(sq) != 0;
     if (const char* wr = getenv("UVHTTP_WS_WALK_REC")) e->wr_rec_on = atoi(wr) != 0;
     if (const char* wm = getenv("UVHTTP_WS_WALK"))
         e->walk_mode = strcmp(wm, "lane") == 0 ? 1 : strcmp(wm, "wave") == 0 ? 2 : 0;
     if (const char* tc = getenv("UVHTTP_WS_TIME_CHAIN")) e->time_chain = atoi(tc) != 0;
-    if (const char* cr = getenv("UVHTTP_WS_COMPACT_RECS")) e->compact_recs = atoi(cr) != 0;
     if (const char* sp2 = getenv("UVHTTP_WS_SPEC")) e->spec_on = atoi(sp2) != 0;
     if (const char* sm = getenv("UVHTTP_WS_SPEC_MAX")) e->spec_max_avg = strtoull(sm, nullptr, 10);
-    if (const char* fa = getenv("UVHTTP_WS_FUSED_AUX")) e->fused_aux = atoi(fa);
     if (const char* sf = getenv("UVHTTP_WS_SUMMARY_FAST")) e->sum_fast = atoi(sf) != 0;
     if (const char* de = getenv("UVHTTP_WS_DESC_EMIT")) e->desc_emit = atoi(de);
     if (const char* tl = getenv("UVHTTP_WS_TILE")) {  // payload tile shape "BxV" (0x0 = auto)
         int tb = 0, tv = 0;
         if (sscanf(tl, "%dx%d", &tb, &tv) == 2) (void)uvhttp_ws_gpu_engine_set_tile(e, tb, tv);  // (validated)
-    }
-    if (const char* fx = getenv("UVHTTP_WS_FIXUP_BLOCKS")) e->fixup_blocks = (uint32_t)strtoul(fx, nullptr, 10);
-    if (e->fixup_blocks == 0) e->fixup_blocks = 1;
-    if (const char* ft = getenv("UVHTTP_WS_FUSED_TILE")) {
-        int fb = 0, fv = 0;
-        if (sscanf(ft, "%dx%d", &fb, &fv) == 2) {
-            e->fused_block = fb;
-            e->fused_vpt = fv;
-        }
     }
 }
 #endif
@@ -5913,7 +5724,6 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     if (!e) return UVHTTP_WS_GPU_ENOMEM;
     e->device = device;
     // the product configuration (each choice measured: DESIGN.md §4-5)
-    e->store_aux = 18;
     e->max_polls = kMaxPolls;
     e->fused_max_avg = kFusedMaxAvg;
     // the fused path scans its records with k_plan's look-back (C4: 133-136 us per step against
@@ -5922,16 +5732,13 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     e->plan_wide = 0;  // 1024-thread blocks measured slower on C4 (1690 vs 1785 GiB/s, r03p7)
     e->build_frames_max = 4096;
     e->wr_rec_on = 1;
-    e->compact_recs = 0;
     e->spec_on = 1;
     e->spec_max_avg = kFusedMaxAvg;
-    e->fused_aux = 18;
-    e->fixup_blocks = 1024;
     e->sum_fast = 1;
-    // 3: in place the scan and k_desc_emit rebuild the info bytes from the records (C4 step 114.0
+    // 2: in place the scan and k_desc_emit rebuild the info bytes from the records (C4 step 114.0
     // vs 115.9 us with them left by the payload pass, profiles/r06h_desc_emit_ab_*.txt); compact
     // the speculative pass leaves them (123.9 vs 126.9 us, profiles/r06j_desc_emit_compact_ab.txt)
-    e->desc_emit = 3;
+    e->desc_emit = 2;
     e->stream_spec = 1;
     {
         int prev = 0;
@@ -6179,8 +5986,8 @@ int uvhttp_ws_gpu_engine_set_stamps(uvhttp_ws_gpu_engine_t* e, int enable) {
         int prev = 0;
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(e->device);
-        hipError_t h = hipMalloc(&e->stamp_mem, kStampAlloc * 8);
-        if (h == hipSuccess) h = hipMemset(e->stamp_mem, 0, kStampAlloc * 8);
+        hipError_t h = hipMalloc(&e->stamp_mem, kStampWords * 8);
+        if (h == hipSuccess) h = hipMemset(e->stamp_mem, 0, kStampWords * 8);
         if (h == hipSuccess) h = hipDeviceSynchronize();
         (void)hipSetDevice(prev);
         if (h != hipSuccess) {
@@ -6303,18 +6110,6 @@ int uvhttp_ws_gpu_stamp_simulate(uint64_t* ring, uint32_t epoch, uint32_t kind, 
     return UVHTTP_WS_GPU_OK;
 }
 
-#ifdef UVWS_PLAN_PHASES
-// experiment builds only: copy k_plan's per-block phase words (8 per block) and clear them
-extern "C" int uvhttp_ws_gpu_engine_debug_phases(uvhttp_ws_gpu_engine_t* e, uint64_t* out, uint32_t blocks) {
-    if (!e || !e->stamp_mem || blocks > 8192) return UVHTTP_WS_GPU_EINVAL;
-    (void)hipDeviceSynchronize();
-    hipError_t h = hipMemcpy(out, e->stamp_mem + kStampWords, 64ull * blocks, hipMemcpyDeviceToHost);
-    if (h == hipSuccess) h = hipMemset(e->stamp_mem + kStampWords, 0, 8 * kPhaseWords);
-    if (h == hipSuccess) h = hipDeviceSynchronize();
-    return h == hipSuccess ? 0 : UVHTTP_WS_GPU_ELAUNCH;
-}
-#endif
-
 static int timing_begin(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
     if (!e->timing || e->capturing) return -1;
     // a timed marker between two kernels idles the device for a few us (the CP drains the
@@ -6401,17 +6196,6 @@ static void launch_plan(uvhttp_ws_gpu_engine_t* e, BatchArgs& a, uint32_t n_cap,
         const uint64_t max_blocks = a.recs ? 256 : 512;
         fpt = 1;
         while (fpt < 16 && ((uint64_t)n_cap + kBlock * fpt - 1) / (kBlock * fpt) > max_blocks) fpt *= 2;
-    }
-    a.no_ticket = e->plan_no_ticket;
-    if (a.recs && e->plan_wide >= 2) {
-        // records, A/B (UVHTTP_WS_PLAN_WIDE=2 / 3): 512-thread blocks, 8 or 16 frames per lane
-        const int f5 = e->plan_wide == 3 ? 16 : 8;
-        const uint32_t per5 = 512u * (uint32_t)f5;
-        a.plan_frames = per5;
-        const uint32_t g5 = n_cap ? (n_cap + per5 - 1) / per5 : 1;
-        if (f5 == 8) hipLaunchKernelGGL((k_plan<8, 512>), dim3(g5), dim3(512), 0, s, a, d_desc, d_msgs, e->ws);
-        else hipLaunchKernelGGL((k_plan<16, 512>), dim3(g5), dim3(512), 0, s, a, d_desc, d_msgs, e->ws);
-        return;
     }
     if (a.recs && e->plan_wide) {
         // records: 1024-thread blocks, so the per-lane state-machine chain is 4x shorter at
@@ -6572,15 +6356,11 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         // 16 KiB tiles at every fused frame size: the tile's LDS staging, parse and barriers
         // are paid per tile, so the fused pass wants larger tiles than the plain payload
         // kernel (r03p34: 256x4 97.9 us on C4, 256x2 112.6, 64x1 182.7; r03p35: 32 KiB tiles
-        // lose, 256x8 +16 %, 512x4 +5 %)
+        // lose, 256x8 +16 %, 512x4 +5 %); an explicit shape (set_tile) holds here too
         int fb = e->tile_block, fv = e->tile_vpt;
         if (!fb) {
             fb = 256;
             fv = 4;
-        }
-        if (e->fused_block) {
-            fb = e->fused_block;
-            fv = e->fused_vpt;
         }
         const uint64_t ft = (uint64_t)fb * fv * 16;
         const uint64_t f_tiles = (b->wire_len + ft - 1) / ft;
@@ -6590,11 +6370,10 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         // data frame — stride >= kSumMinStride — and no message can reach max_message_size: the
         // bound below) and leaves one TilePart per tile; k_sum_tail writes the summary and undoes
         // a failure.  No records, no k_plan, no descriptors.
-        const bool sum_fast = !d_desc && fb == 256 && fv == 4 && e->fused_aux == 18 && sum_ok(e, b);
+        const bool sum_fast = !d_desc && fb == 256 && fv == 4 && sum_ok(e, b);
         // descriptors under the same bounds: records + info bytes, the info-byte scan, then the
         // parallel descriptor pass (k_desc_emit) instead of k_plan on the records + k_fixup
-        const bool desc_emit = d_desc && e->desc_emit && fb == 256 && fv == 4 && e->fused_aux == 18 &&
-                               sum_ok(e, b);
+        const bool desc_emit = d_desc && e->desc_emit && fb == 256 && fv == 4 && sum_ok(e, b);
         if (desc_emit) {
             // (desc_emit >= 2: no info bytes — the scan and k_desc_emit rebuild them from the records)
             const bool from_rec = e->desc_emit >= 2;
@@ -6602,10 +6381,10 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
             for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
                 const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
                 if (from_rec)
-                    hipLaunchKernelGGL((k_unmask_stride<256, 4, 18, kLeaveRec>), dim3(grid_p), dim3(256), 0, s, a,
+                    hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveRec>), dim3(grid_p), dim3(256), 0, s, a,
                                        e->ws, tb);
                 else
-                    hipLaunchKernelGGL((k_unmask_stride<256, 4, 18, kLeaveBoth>), dim3(grid_p), dim3(256), 0, s, a,
+                    hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveBoth>), dim3(grid_p), dim3(256), 0, s, a,
                                        e->ws, tb);
             }
             timing_end(e, stk, s);
@@ -6631,7 +6410,7 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
             const int stk = timing_begin(e, s);
             for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
                 const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, 18, kLeaveInfo>), dim3(grid_p), dim3(256), 0, s, a,
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveInfo>), dim3(grid_p), dim3(256), 0, s, a,
                                    e->ws, tb);
             }
             timing_end(e, stk, s);
@@ -6651,19 +6430,12 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
             const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
 #define UVWS_FUSED(B, V)                                                                         \
-    if (fb == B && fv == V) {                                                                    \
-        if (B == 256 && V == 4 && e->fused_aux == 2)                                             \
-            hipLaunchKernelGGL((k_unmask_stride<256, 4, 2>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);  \
-        else if (B == 256 && V == 4 && e->fused_aux == 0)                                        \
-            hipLaunchKernelGGL((k_unmask_stride<256, 4, 0>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);  \
-        else if (B == 256 && V == 4 && e->fused_aux == 16)                                       \
-            hipLaunchKernelGGL((k_unmask_stride<256, 4, 16>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb); \
-        else                                                                                     \
-            hipLaunchKernelGGL((k_unmask_stride<B, V>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb); \
-    } else
+    if (fb == B && fv == V)                                                                      \
+        hipLaunchKernelGGL((k_unmask_stride<B, V>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);  \
+    else
+            // (the shapes set_tile accepts)
             UVWS_FUSED(64, 1) UVWS_FUSED(64, 2) UVWS_FUSED(64, 4) UVWS_FUSED(128, 1)
-            UVWS_FUSED(128, 2) UVWS_FUSED(256, 1) UVWS_FUSED(256, 2) UVWS_FUSED(256, 4)
-            UVWS_FUSED(256, 8) UVWS_FUSED(512, 4) UVWS_FUSED(512, 8) {
+            UVWS_FUSED(128, 2) UVWS_FUSED(256, 1) UVWS_FUSED(256, 2) UVWS_FUSED(256, 4) {
                 if (prev != e->device) (void)hipSetDevice(prev);
                 return set_err(e, UVHTTP_WS_GPU_EINVAL, "unsupported fused tile shape", hipSuccess);
             }
@@ -6682,8 +6454,8 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
                                d_msgs, e->ws);
         }
         const uint32_t fx = (a.n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_fixup, dim3(fx < e->fixup_blocks ? fx : e->fixup_blocks), dim3(kBlock), 0, s,
-                           a, d_desc, e->ws);
+        hipLaunchKernelGGL(k_fixup, dim3(fx < kFixupBlocks ? fx : kFixupBlocks), dim3(kBlock), 0, s, a, d_desc,
+                           e->ws);
         hipError_t hf = hipGetLastError();
         if (prev != e->device) (void)hipSetDevice(prev);
         if (hf != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hf);
@@ -6718,22 +6490,21 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         // frame, another length, ...) is decoded again by k_plan + k_spec_fix, which otherwise
         // return at once (ctl[kCtlGate])
         const bool sum_c = no_desc && sum_ok(e, b) && arena_cap / spec_p >= a.n;
-        // with descriptors under the same bounds: the records pass, the scan and k_sum_msgs
-        // rebuilding the info bytes from the records, k_sum_msgs also writing the descriptors
+        // with descriptors under the same bounds: the pass leaves records and info bytes, the
+        // scan reads the info bytes, k_sum_msgs also writes the descriptors from the records
         const bool desc_c = !no_desc && e->desc_emit && sum_ok(e, b) && arena_cap / spec_p >= a.n;
         if (sum_c) a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);  // (the info bytes)
         const int stk = timing_begin(e, s);
-        const bool both = desc_c && e->desc_emit != 2;  // (records + info bytes from the pass)
         for (uint64_t tb = 0; tb < s_tiles; tb += (1ull << 24)) {
             const uint32_t grid_s = (uint32_t)((s_tiles - tb) < (1ull << 24) ? (s_tiles - tb) : (1ull << 24));
-            if (both)
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, kSpecCompact, kLeaveBoth>), dim3(grid_s), dim3(256), 0,
+            if (desc_c)
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveBoth>), dim3(grid_s), dim3(256), 0,
                                    s, a, e->ws, tb);
             else if (sum_c)
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, kSpecCompact, kLeaveInfo>), dim3(grid_s), dim3(256), 0, s, a,
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveInfo>), dim3(grid_s), dim3(256), 0, s, a,
                                    e->ws, tb);
             else
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, kSpecCompact>), dim3(grid_s), dim3(256), 0, s, a, e->ws, tb);
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, true>), dim3(grid_s), dim3(256), 0, s, a, e->ws, tb);
         }
         timing_end(e, stk, s);
         if (sum_c) {
@@ -6745,19 +6516,12 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
             a.gate = 1;
         } else if (desc_c) {
             const uint32_t n_parts = (a.n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt);
-            if (both) {
-                BatchArgs ai = a;  // the scan reads the info bytes
-                ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
-                hipLaunchKernelGGL((k_sum_scan<true, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0, s,
-                                   ai, e->ws);
-                hipLaunchKernelGGL((k_sum_msgs<false, true>), dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts,
-                                   d_msgs, d_desc);
-            } else {
-                hipLaunchKernelGGL((k_sum_scan<true, UVHTTP_WS_STAMP_SUM_SCAN, true>), dim3(n_parts), dim3(kBlock),
-                                   0, s, a, e->ws);
-                hipLaunchKernelGGL((k_sum_msgs<true, true>), dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts,
-                                   d_msgs, d_desc);
-            }
+            BatchArgs ai = a;  // the scan reads the info bytes
+            ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
+            hipLaunchKernelGGL((k_sum_scan<true, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0, s, ai,
+                               e->ws);
+            hipLaunchKernelGGL(k_sum_msgs<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_msgs,
+                               d_desc);
             a.gate = 1;  // (the fall-back's k_plan reads the same records)
         }
         launch_plan(e, a, a.n, d_desc, d_msgs, s);
@@ -6771,25 +6535,6 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         if (prev != e->device) (void)hipSetDevice(prev);
         if (hs != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hs);
         return UVHTTP_WS_GPU_OK;
-    }
-    // compact stride batches of small frames: a records-only pass over the wire (linear reads;
-    // k_plan's scattered header gather costs as much as reading everything),
-    // then k_plan on the records (UVHTTP_WS_COMPACT_RECS=1; off by default)
-    const uint64_t cavg = a.n ? b->wire_len / a.n : 0;
-    const bool rec_compact = arena && e->compact_recs && !b->frame_off && a.n > 0 &&
-                             cavg <= e->fused_max_avg && cavg < kScatterAvg && e->compact_mode != 1 &&
-                             b->frame_stride >= kFusedMinStride && b->wire_len > 0 &&
-                             b->wire_len < (1ull << 52) &&
-                             (uint64_t)(a.n - 1) <= (b->wire_len - 1) / b->frame_stride;
-    if (rec_compact) {
-        a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
-        a.stride_inv = 1.0 / (double)b->frame_stride;
-        constexpr uint64_t kRt = 256ull * 4 * 16;
-        const uint64_t r_tiles = (b->wire_len + kRt - 1) / kRt;
-        for (uint64_t tb = 0; tb < r_tiles; tb += (1ull << 24)) {
-            const uint32_t grid_r = (uint32_t)((r_tiles - tb) < (1ull << 24) ? (r_tiles - tb) : (1ull << 24));
-            hipLaunchKernelGGL((k_unmask_stride<256, 4, -1>), dim3(grid_r), dim3(256), 0, s, a, e->ws, tb);
-        }
     }
     launch_plan(e, a, a.n, d_desc, d_msgs, s);
     // payload kernel tile shape: explicit (set_tile) or by average wire bytes per frame
@@ -6829,10 +6574,7 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
         const uint32_t grid_p = (uint32_t)((n_ptiles - tb) < max_tiles ? (n_ptiles - tb) : max_tiles);
 #define UVWS_LAUNCH(B, V)                                                                        \
     if (blk == B && vpt == V) {                                                                  \
-        if (!arena && e->store_aux == 18)                                                        \
-            hipLaunchKernelGGL((k_unmask_inplace<B, V, 18>), dim3(grid_p), dim3(B), 0, s, a,     \
-                               d_desc, e->ws, tb);                                               \
-        else if (!arena)                                                                         \
+        if (!arena)                                                                              \
             hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, \
                                e->ws, tb);                                                       \
         else if (scatter)                                                                        \
@@ -6918,6 +6660,29 @@ static int reserve_streams(uvhttp_ws_gpu_engine_t* e, uint32_t frames, uint32_t 
     return UVHTTP_WS_GPU_OK;
 }
 
+// The layout of the speculative stream decode's scratch (sp_mem) for `streams` connections and
+// `tiles` kSpecT-byte wire tiles: the one place its offsets are computed (reserve_spec sizes the
+// block from it, the decode fills SpecArgs from it with the reserved capacities).
+struct SpecLayout {
+    size_t conns;      // SpecConn[streams]
+    size_t blk;        // uint32_t[streams / kBlock + 2] block counts
+    size_t blk_pre;    // uint32_t[streams / kBlock + 2] their prefixes
+    size_t conn_tile;  // uint64_t[tiles + 1] tile claims
+    size_t tiles;      // SpecTile[tiles + 1]
+    size_t bytes;
+};
+static SpecLayout spec_layout(uint32_t streams, uint64_t tiles) {
+    const size_t n_blk = (size_t)streams / kBlock + 2;
+    SpecLayout l;
+    l.conns = 0;
+    l.blk = align_up((size_t)streams * sizeof(SpecConn), 256);
+    l.blk_pre = l.blk + n_blk * sizeof(uint32_t);
+    l.conn_tile = align_up(l.blk_pre + n_blk * sizeof(uint32_t), 256);
+    l.tiles = align_up(l.conn_tile + (size_t)(tiles + 1) * sizeof(uint64_t), 256);
+    l.bytes = align_up(l.tiles + (size_t)(tiles + 1) * sizeof(SpecTile), 256);
+    return l;
+}
+
 // the speculative stream decode's scratch (zeroed: no tile claim matches a live epoch)
 static int reserve_spec(uvhttp_ws_gpu_engine_t* e, uint32_t streams, uint64_t tiles, hipStream_t s) {
     if (e->sp_mem && streams <= e->sp_streams && tiles <= e->sp_tiles) return UVHTTP_WS_GPU_OK;
@@ -6925,10 +6690,7 @@ static int reserve_spec(uvhttp_ws_gpu_engine_t* e, uint32_t streams, uint64_t ti
         return set_err(e, UVHTTP_WS_GPU_EINVAL, "stream scratch too small for a captured call", hipSuccess);
     const uint32_t ns = streams > e->sp_streams ? streams : e->sp_streams;
     const uint64_t nt = tiles > e->sp_tiles ? tiles : e->sp_tiles;
-    const size_t o_blk = align_up((size_t)ns * sizeof(SpecConn), 256);
-    const size_t o_tile = align_up(o_blk + ((size_t)ns / kBlock + 2) * 8, 256);  // (counts, prefixes)
-    const size_t o_trec = align_up(o_tile + (size_t)(nt + 1) * 8, 256);
-    const size_t bytes = align_up(o_trec + (size_t)(nt + 1) * sizeof(SpecTile), 256);
+    const size_t bytes = spec_layout(ns, nt).bytes;
     int prev = 0;
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(e->device);
@@ -7032,10 +6794,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     w.stamp = (e->stamp_on && !e->capturing) ? e->stamp_mem : nullptr;
     w.cas_claims = e->captured_ever ? 1u : 0u;
     w.max_polls = e->max_polls;
-    w.no_ticket = e->plan_no_ticket;
-    w.nt_stores = e->stream_nt ? 1u : 0u;
     w.desc_scan = 0;
-    w.nt_loads = e->walk_nt_load ? 1u : 0u;
     w.first_bad = e->ws.first_bad;
     const uint32_t nsb = (n_streams + kBlock - 1) / kBlock;
     const uint32_t nwb = (n_streams + kBlock / 64 - 1) / (kBlock / 64);
@@ -7057,15 +6816,13 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
         sa.read_end = d_read_end;
         sa.n_reads_total = n_reads_total;
         char* sb = (char*)e->sp_mem;
-        sa.conns = (SpecConn*)sb;
-        sa.blk = (uint32_t*)(sb + align_up((size_t)e->sp_streams * sizeof(SpecConn), 256));
-        sa.blk_pre = sa.blk + ((size_t)e->sp_streams / kBlock + 2);
+        const SpecLayout sl = spec_layout(e->sp_streams, e->sp_tiles);
+        sa.conns = (SpecConn*)(sb + sl.conns);
+        sa.blk = (uint32_t*)(sb + sl.blk);
+        sa.blk_pre = (uint32_t*)(sb + sl.blk_pre);
         sa.n_blk = nsb;
-        sa.conn_tile = (uint64_t*)(sb + align_up(align_up((size_t)e->sp_streams * sizeof(SpecConn), 256) +
-                                                     ((size_t)e->sp_streams / kBlock + 2) * 4, 256));
-        sa.tiles = (SpecTile*)(sb + align_up(align_up(align_up((size_t)e->sp_streams * sizeof(SpecConn), 256) +
-                                                            ((size_t)e->sp_streams / kBlock + 2) * 8, 256) +
-                                                   (size_t)(e->sp_tiles + 1) * 8, 256));
+        sa.conn_tile = (uint64_t*)(sb + sl.conn_tile);
+        sa.tiles = (SpecTile*)(sb + sl.tiles);
         sa.n_tiles = sp_tiles;
         sa.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
         sa.desc = d_desc;
@@ -7167,14 +6924,9 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     for (uint64_t tb = 0; tb < n_ptiles; tb += max_tiles) {
         const uint32_t grid_p = (uint32_t)((n_ptiles - tb) < max_tiles ? (n_ptiles - tb) : max_tiles);
 #define UVWS_LAUNCH(B, V)                                                                        \
-    if (blk == B && vpt == V) {                                                                  \
-        if (e->store_aux == 18)                                                                  \
-            hipLaunchKernelGGL((k_unmask_inplace<B, V, 18>), dim3(grid_p), dim3(B), 0, s, a,     \
-                               d_desc, e->ws, tb);                                               \
-        else                                                                                     \
-            hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, \
-                               e->ws, tb);                                                       \
-    } else
+    if (blk == B && vpt == V)                                                                    \
+        hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws, tb); \
+    else
         UVWS_LAUNCH(64, 1) UVWS_LAUNCH(64, 2) UVWS_LAUNCH(64, 4) UVWS_LAUNCH(128, 1)
         UVWS_LAUNCH(128, 2) UVWS_LAUNCH(256, 1) UVWS_LAUNCH(256, 2) UVWS_LAUNCH(256, 4) {}
 #undef UVWS_LAUNCH
