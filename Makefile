@@ -22,7 +22,15 @@ CFLAGS := -O2 -DNDEBUG -fPIC -std=gnu11 -Iinclude -Wall -Wextra -Werror
 
 all: $(LIB) $(TESTLIB) oracle ctests probes
 
-$(BUILD)/ws_gpu.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h
+ENGINE_INT := uvhttp_amd/csrc/ws_engine_int.h
+UTF8_RULES := uvhttp_amd/csrc/utf8_rules.h
+
+$(BUILD)/ws_gpu.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+# UTF-8 validation of TEXT messages: no environment switches, so one object serves both libraries
+$(BUILD)/utf8_gpu.o: uvhttp_amd/csrc/utf8_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT) $(UTF8_RULES)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
@@ -38,7 +46,7 @@ $(BUILD)/ws_batcher_testhooks.o: uvhttp_amd/csrc/ws_batcher.hip include/uvhttp_w
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -DUVWS_TEST_HOOKS $(EXP) -c -o $@ $<
 
-$(BUILD)/ws_gpu_exp.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h
+$(BUILD)/ws_gpu_exp.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXP) -c -o $@ $<
 
@@ -46,11 +54,11 @@ $(BUILD)/tls_gpu_exp.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXP) -c -o $@ $<
 
-$(BUILD)/ws_host_exp.o: uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
+$(BUILD)/ws_host_exp.o: uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h $(UTF8_RULES)
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) $(EXP) -c -o $@ $<
 
-$(BUILD)/ws_host.o: uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
+$(BUILD)/ws_host.o: uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h $(UTF8_RULES)
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c -o $@ $<
 
@@ -59,12 +67,12 @@ $(BUILD)/ws_batcher_group.o: uvhttp_amd/csrc/ws_batcher_group.cpp include/uvhttp
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -fPIC -std=c++17 -Iinclude -Wall -Wextra -Werror -c -o $@ $<
 
-$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
+$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
         $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
-$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
+$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
             $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -89,10 +97,11 @@ tools/bin/copy_probe: tools/copy_probe.cpp $(BUILD)/ws_host.o
 	@mkdir -p tools/bin
 	g++ -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude -o $@ $^ -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
-asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip
+asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_gpu.s uvhttp_amd/csrc/ws_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/tls_gpu.s uvhttp_amd/csrc/tls_gpu.hip
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/utf8_gpu.s uvhttp_amd/csrc/utf8_gpu.hip
 
 clean:
 	rm -rf $(BUILD) uvhttp_amd/lib

@@ -435,6 +435,66 @@ int uvhttp_ws_gpu_decode_compact(uvhttp_ws_gpu_engine_t* eng, const uvhttp_ws_ba
                                  uvhttp_ws_message_desc_t* d_msgs,
                                  uvhttp_ws_batch_summary_t* d_summary, void* stream);
 
+/* ---- UTF-8 validation of TEXT messages (RFC 6455 §5.6, §8.1) --------------------------- */
+/* The reference never checks that a TEXT message is UTF-8; a conforming endpoint must fail the
+ * connection with close code 1007 when it is not.  This is a separate, opt-in call made after a
+ * compact decode (every message, a fragmented one included, is then one contiguous arena
+ * range): it reads each arena byte once and writes one 4-byte verdict per message plus a
+ * 16-byte summary.  No decode or deliver call changes what it delivers; the caller looks at the
+ * verdicts and closes with 1007. */
+#define UVHTTP_WS_UTF8_VALID     0  /* complete TEXT message, well-formed UTF-8 (RFC 3629) */
+#define UVHTTP_WS_UTF8_INVALID   1  /* not UTF-8: overlong, surrogate, > U+10FFFF, stray or missing
+                                       continuation, truncated at the message end */
+#define UVHTTP_WS_UTF8_NOT_TEXT  2  /* opcode != 1: not examined */
+#define UVHTTP_WS_UTF8_PREFIX    3  /* the open message only: valid so far; `tail` bytes (0..3) at its
+                                       end start a sequence that some continuation can complete */
+#define UVHTTP_WS_UTF8_BAD_RANGE 4  /* [arena_off, arena_off+len) not inside data_len: not read */
+
+typedef struct { uint8_t status; uint8_t tail; uint16_t reserved; } uvhttp_ws_utf8_verdict_t;   /* 4 B */
+typedef struct {
+    uint32_t n_text;         /* TEXT messages judged (the open one included) */
+    uint32_t n_invalid;      /* of them INVALID or BAD_RANGE */
+    uint32_t first_invalid;  /* lowest such message index, 0xFFFFFFFF if none */
+    uint32_t open_verdict;   /* status | tail << 8 of the open message's entry, 0 if none */
+} uvhttp_ws_utf8_summary_t;                                                                    /* 16 B */
+
+/* All pointers are device pointers (d_data 16-byte aligned, d_msgs 8, the others 4); asynchronous
+ * on `stream`, under the engine's rule for calls from different streams (above).
+ *   After a compact decode: d_data = d_arena, data_len = arena_cap (or any bound >= the
+ *   summary's arena_bytes), d_msgs and d_batch_summary = the decode's d_msgs and d_summary;
+ *   n_msgs is ignored.  The kernels read n_messages and pending_bytes from device memory, so no
+ *   host sync sits between decode and validation.  Entries [0, n_messages) are judged as
+ *   complete messages; when pending_bytes != 0, entry [n_messages] (the open message) is judged
+ *   as a prefix: PREFIX with `tail`, or INVALID as soon as no continuation could make it valid
+ *   (ED A0, F4 90, E0 9F are invalid at once; E0, F0 9F 98, C2 are PREFIX with tail 1, 3, 1).  A
+ *   failed batch judges exactly the messages its summary counts.  Entries past max_msgs are
+ *   neither read nor judged.
+ *   Generic form: d_batch_summary == NULL; the caller's own table of n_msgs complete messages is
+ *   judged (opcode 1 where a check is wanted).  Ranges must ascend in arena_off and must not
+ *   overlap; gaps are allowed.  A table that breaks the rule gets unspecified verdicts, but
+ *   nothing outside [0, data_len) is read.
+ * max_msgs is the capacity of d_verdict (entries); nothing past it is read or written.  EINVAL
+ * for NULL or misaligned arguments and for n_msgs > max_msgs.  Graph-capturable: no allocation,
+ * no epoch-tagged scratch.  A zero-length TEXT message is VALID.  To continue an open message
+ * on the host, seed uvhttp_ws_utf8_feed's state with the last `tail` bytes of its arena range. */
+int uvhttp_ws_gpu_validate_utf8(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_data, uint64_t data_len,
+                                const uvhttp_ws_message_desc_t* d_msgs, uint32_t max_msgs,
+                                const uvhttp_ws_batch_summary_t* d_batch_summary, uint32_t n_msgs,
+                                uvhttp_ws_utf8_verdict_t* d_verdict,
+                                uvhttp_ws_utf8_summary_t* d_utf8_summary, void* stream);
+
+/* Host UTF-8 check (plain C, incremental): for drop-in users who stay on
+ * uvhttp_ws_process_data, and to continue an open message after the device judged its prefix.
+ * A zeroed state is the start of a message.  feed returns 0, or -1 as soon as the bytes fed so
+ * far cannot be extended to valid UTF-8 (fail-fast, the same rule as the device's PREFIX
+ * verdicts); the state is then unspecified.  finish returns 0 iff no sequence is open (the
+ * message may end here).  After feed, pend[0, n) are the bytes of the open sequence — so the
+ * state after a device PREFIX verdict is n = tail, pend = the last `tail` bytes of the
+ * message's arena range. */
+typedef struct { uint8_t pend[3]; uint8_t n; } uvhttp_ws_utf8_state_t;   /* zero = start of message */
+int uvhttp_ws_utf8_feed(uvhttp_ws_utf8_state_t* st, const uint8_t* data, size_t len);
+int uvhttp_ws_utf8_finish(const uvhttp_ws_utf8_state_t* st);
+
 /* Unmask only (no framing): data[i] ^= key[i % 4] for a device buffer — the batched form
  * of uvhttp_ws_apply_mask for callers that parsed headers themselves. */
 int uvhttp_ws_gpu_apply_mask(uvhttp_ws_gpu_engine_t* eng, uint8_t* d_data, uint64_t len,

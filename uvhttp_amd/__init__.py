@@ -73,6 +73,28 @@ class BatchSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Utf8Verdict(C.Structure):
+    """uvhttp_ws_utf8_verdict_t (4 B)."""
+    _fields_ = [("status", C.c_uint8), ("tail", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class Utf8Summary(C.Structure):
+    """uvhttp_ws_utf8_summary_t (16 B)."""
+    _fields_ = [("n_text", C.c_uint32), ("n_invalid", C.c_uint32), ("first_invalid", C.c_uint32),
+                ("open_verdict", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Utf8State(C.Structure):
+    """uvhttp_ws_utf8_state_t (4 B): the open sequence's bytes; zero = start of a message."""
+    _fields_ = [("pend", C.c_uint8 * 3), ("n", C.c_uint8)]
+
+
+UTF8_VALID, UTF8_INVALID, UTF8_NOT_TEXT, UTF8_PREFIX, UTF8_BAD_RANGE = range(5)
+
+
 class Stream(C.Structure):
     """uvhttp_ws_stream_t (64 B)."""
     _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("recv_buffer_size", C.c_uint64),
@@ -293,6 +315,9 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_ws_gpu_decode_compact": (C.c_int, [vp, C.POINTER(Batch), vp, u64, vp, vp, vp,
                                                    vp]),
         "uvhttp_ws_gpu_apply_mask": (C.c_int, [vp, vp, u64, vp, vp]),
+        "uvhttp_ws_gpu_validate_utf8": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
+        "uvhttp_ws_utf8_feed": (C.c_int, [C.POINTER(Utf8State), vp, C.c_size_t]),
+        "uvhttp_ws_utf8_finish": (C.c_int, [C.POINTER(Utf8State)]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -410,6 +435,19 @@ def apply_mask(data: bytearray, key, length=None, null=None):
     kb = (C.c_uint8 * 4).from_buffer_copy(bytes(key)) if key else None
     L.uvhttp_ws_apply_mask(None if null == "data" else buf, n, None if null == "key" else kb)
     return data
+
+
+def utf8_feed(state: Utf8State, data) -> int:
+    """uvhttp_ws_utf8_feed: continue a TEXT message's UTF-8 check with `data`; 0, or -1 as soon
+    as no continuation could make the message valid.  Utf8State() starts a message."""
+    data = bytes(data)
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+    return int(lib().uvhttp_ws_utf8_feed(C.byref(state), buf, len(data)))
+
+
+def utf8_finish(state: Utf8State) -> int:
+    """uvhttp_ws_utf8_finish: 0 iff the message may end here (no sequence is open)."""
+    return int(lib().uvhttp_ws_utf8_finish(C.byref(state)))
 
 
 class WsConnection:
@@ -694,6 +732,38 @@ class GpuEngine:
         self._check(self._L.uvhttp_ws_gpu_apply_mask(
             self.h, C.c_void_p(data.data_ptr() + offset), n, kb, self._stream(stream)),
             "apply_mask")
+
+    def validate_utf8(self, data, msgs, max_msgs, batch_summary=None, n_msgs=0, verdict=None,
+                      summary=None, stream=None):
+        """uvhttp_ws_gpu_validate_utf8: judge the TEXT messages of `msgs` (device uint8 tensor of
+        uvhttp_ws_message_desc_t) over the device bytes `data`.  With batch_summary (a compact
+        decode's summary tensor) the decode's own message count is read on the device; without,
+        the first n_msgs entries are judged as complete messages.  Returns (verdict, summary)
+        device tensors: max_msgs 4-byte verdicts and the 16-byte uvhttp_ws_utf8_summary_t."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if verdict is None:
+            verdict = t.zeros(max(1, max_msgs) * C.sizeof(Utf8Verdict), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(Utf8Summary), dtype=t.uint8, device=dev)
+        self._check(self._L.uvhttp_ws_gpu_validate_utf8(
+            self.h, C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(msgs.data_ptr()), max_msgs,
+            C.c_void_p(batch_summary.data_ptr() if batch_summary is not None else None), n_msgs,
+            C.c_void_p(verdict.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
+            "validate_utf8")
+        return verdict, summary
+
+    @staticmethod
+    def read_utf8(verdict, n):
+        """host copy of the first n verdicts: numpy records (status, tail, reserved)"""
+        import numpy as np
+        dt = np.dtype([("status", "u1"), ("tail", "u1"), ("reserved", "<u2")])
+        return verdict[: n * 4].cpu().numpy().view(dt)
+
+    @staticmethod
+    def read_utf8_summary(summary) -> dict:
+        raw = bytes(summary.cpu().numpy().tobytes())
+        return Utf8Summary.from_buffer_copy(raw).as_dict()
 
     def gen_frames(self, wire, n_frames, payload_len, seed, opcode0=2, fragmented=False,
                    force_keys=False, stream=None, first=0, count=None, total=None):

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "uvhttp_ws_amd.h"
+#include "ws_engine_int.h"
 
 namespace {
 
@@ -6180,6 +6181,27 @@ static void call_begin(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
     }
     e->last_stream = s;
     e->have_last = 1;
+}
+
+// ws_engine_int.h: the same call frame for sources outside this file (utf8_gpu.hip)
+int uvws_call_enter(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (prev != e->device) (void)hipSetDevice(e->device);
+    call_begin(e, s);
+    return prev;
+}
+
+int uvws_call_leave(uvhttp_ws_gpu_engine_t* e, int prev_device, const char* what) {
+    e->capturing = 0;
+    const hipError_t h = hipGetLastError();
+    if (prev_device != e->device) (void)hipSetDevice(prev_device);
+    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, what, h);
+    return UVHTTP_WS_GPU_OK;
+}
+
+int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what) {
+    return set_err(e, code, what, hipSuccess);
 }
 
 // k_plan launch: frames per lane chosen so the grid stays within ~512 blocks — every block

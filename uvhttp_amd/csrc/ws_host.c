@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "utf8_rules.h"
 #include "uvhttp_ws_amd.h"
 
 static uvhttp_ws_amd_context_resolver g_resolver = NULL;
@@ -618,4 +619,47 @@ __attribute__((visibility("hidden"))) void uvhttp_ws_amd_copy_stream(void* dst, 
 #else
     memcpy(dst, src, len);
 #endif
+}
+
+/* ---- UTF-8 check of TEXT payloads (RFC 6455 §5.6; the reference has none) --------------- */
+/* The state is the open sequence itself: pend[0, n) are its bytes so far, in order.  So the
+ * state after a device PREFIX verdict (uvhttp_ws_gpu_validate_utf8) is n = tail and pend = the
+ * last `tail` bytes of the message's arena range.  The rules are utf8_rules.h's, shared with
+ * the device kernels; runs of ASCII are skipped eight bytes at a time. */
+int uvhttp_ws_utf8_feed(uvhttp_ws_utf8_state_t* st, const uint8_t* data, size_t len) {
+    if (st == NULL || st->n > 3 || (data == NULL && len != 0)) return -1;
+    uint32_t p1 = 0, p2 = 0, p3 = 0;
+    if (st->n == 1) {
+        p1 = st->pend[0];
+    } else if (st->n == 2) {
+        p2 = st->pend[0], p1 = st->pend[1];
+    } else if (st->n == 3) {
+        p3 = st->pend[0], p2 = st->pend[1], p1 = st->pend[2];
+    }
+    size_t i = 0;
+    while (i < len) {
+        if (p1 < 0x80u) { /* no sequence open: p2, p3 cannot matter after an ASCII byte */
+            while (i + 8 <= len) {
+                uint64_t w;
+                memcpy(&w, data + i, 8);
+                if (w & 0x8080808080808080ull) break;
+                i += 8;
+                p1 = p2 = p3 = 0;
+            }
+            if (i == len) break;
+        }
+        const uint32_t b = data[i++];
+        if (uvws_utf8_bad(b, p1, p2, p3)) return -1;
+        p3 = p2, p2 = p1, p1 = b;
+    }
+    const uint32_t n = uvws_utf8_open(p1, p2, p3);
+    st->n = (uint8_t)n;
+    st->pend[0] = (uint8_t)(n == 1 ? p1 : n == 2 ? p2 : n == 3 ? p3 : 0);
+    st->pend[1] = (uint8_t)(n == 2 ? p1 : n == 3 ? p2 : 0);
+    st->pend[2] = (uint8_t)(n == 3 ? p1 : 0);
+    return 0;
+}
+
+int uvhttp_ws_utf8_finish(const uvhttp_ws_utf8_state_t* st) {
+    return (st != NULL && st->n == 0) ? 0 : -1;
 }
