@@ -601,6 +601,102 @@ uvhttp_error_t uvhttp_ws_deliver_stream(struct uvhttp_ws_connection* conn, const
                                         const uvhttp_ws_stream_t* s,
                                         const uvhttp_ws_stream_result_t* r);
 
+/* ---- UTF-8 validation of TEXT frames after an in-place or stream decode ------------------ */
+/* uvhttp_ws_gpu_validate_utf8 (above) needs a compact decode.  These calls judge the TEXT
+ * messages where an in-place decode (decode_inplace, the pipelines' submit / wait) or a stream
+ * decode (decode_streams / decode_reads, the batcher) left them: as unmasked payloads inside
+ * the wire, a message's bytes split over frames with headers, control frames and other
+ * connections' bytes in between, and possibly open across calls.  Opt-in, made after the
+ * decode; no decode, deliver, pipeline or batcher call changes what it does.
+ *
+ * Which frames are judged.  Connection s: desc[first_frame, first_frame + n_delivered).  The
+ * streams form reads first_frame and n_delivered from d_results[s] on the device, the in-place
+ * form n_delivered from d_batch_summary (one connection, first_frame 0, nothing carried in), so
+ * no host sync sits between decode and validation.  Failing, SKIPPED and INCOMPLETE frames and
+ * everything after a connection's first failure are neither read nor judged; nor is a
+ * descriptor at or past max_frames (n_frames).  A connection whose result is ERR_CAPACITY or
+ * ERR_LAYOUT judges nothing and is VALID.
+ *
+ * Message membership follows the decoder: a delivered frame with opcode 1 or 2 starts a
+ * message; a delivered CONTINUATION belongs to the message the nearest earlier delivered start
+ * frame of the connection began, or, when there is none, to the carried-in message — opcode
+ * d_streams[s].pending_opcode when pending_bytes != 0, with d_state_in[s] its open sequence
+ * (used only when that opcode is TEXT; d_state_in == NULL means all zero).  FIN ends the
+ * message.  Control frames in between contribute nothing.  Only bytes of TEXT messages are
+ * examined; BINARY payloads may hold anything.
+ *
+ * Verdict, per connection.  Take a TEXT message's bytes in frame order, the carried-in pend
+ * first.  first_invalid is the first frame after which they can no longer be extended to valid
+ * UTF-8 (the fail-fast rule of uvhttp_ws_utf8_feed: ED A0, F4 90, E0 9F and a stray
+ * continuation byte are invalid at the byte that shows it), or the FIN frame of a message that
+ * ends inside a sequence (a zero-length FIN CONTINUATION included).  INVALID is sticky: later
+ * frames do not change first_invalid.  PREFIX: no violation, and a TEXT message is still open
+ * after the last delivered frame; `state` holds its open sequence (0-3 bytes, gathered across
+ * frames when the fragments are tiny).  Passing that state back as d_state_in[s] with the next
+ * call (whose d_streams[s] carries the decoder's pending_opcode / pending_bytes) gives the
+ * verdicts one call over all the bytes would.  VALID otherwise.  n_text_frames counts every
+ * delivered data frame of a TEXT message, those after first_invalid included.
+ * UVHTTP_WS_UTF8_CHECK_CLOSE (RFC 6455 §5.5.1): bytes [2, len) of a delivered CLOSE frame with
+ * payload_len > 2 are judged as one complete message, a violation blames that frame; without
+ * the flag CLOSE frames are ignored.
+ * BAD_RANGE: a judged frame's payload range is not inside [0, wire_len); first_invalid names
+ * it, and it wins over INVALID when it is the earlier frame.  Nothing outside the wire is read.
+ * Delivered frames must ascend in payload_off with the descriptor index (every decode writes
+ * them so); a table that breaks the rule gets unspecified verdicts, but nothing outside the
+ * wire, the descriptors below max_frames and the n_streams entries is read or written.
+ *
+ * All pointers are device pointers: d_wire 16-byte aligned (as uvhttp_ws_batch_t.wire), d_desc,
+ * d_streams, d_results and d_batch_summary 8, the others 4.  EINVAL for NULL (d_state_in
+ * excepted) or misaligned arguments, and for max_frames > 2^28 or n_streams > 2^31.
+ * Asynchronous on `stream` under the engine's stream rule.  The call keeps per-frame scratch
+ * in the engine (36 bytes per descriptor), grown on demand: graph-capturable once one
+ * uncaptured call of the same or a larger shape (max_frames, n_streams) has been made; a
+ * captured call that would allocate fails with ENOMEM. */
+#define UVHTTP_WS_UTF8_CHECK_CLOSE 0x1u   /* flags: also judge CLOSE reasons */
+
+typedef struct {                  /* 16 B, one per connection, device-written */
+    uint32_t first_invalid;       /* desc index (absolute) of the first frame at which the
+                                     connection's text is certainly not UTF-8 (or whose range is
+                                     bad); 0xFFFFFFFF if none */
+    uint32_t n_text_frames;       /* delivered data frames of TEXT messages */
+    uvhttp_ws_utf8_state_t state; /* PREFIX only: the open sequence's bytes (pend[0, n)), i.e. what
+                                     uvhttp_ws_utf8_feed would hold; zero otherwise */
+    uint8_t status;               /* UVHTTP_WS_UTF8_VALID / INVALID / PREFIX / BAD_RANGE */
+    uint8_t reserved[3];
+} uvhttp_ws_utf8_conn_verdict_t;
+
+typedef struct {                  /* 16 B */
+    uint32_t n_text_frames;       /* sum over the connections */
+    uint32_t n_invalid_conns;     /* connections INVALID or BAD_RANGE */
+    uint32_t first_invalid_conn;  /* lowest such connection, 0xFFFFFFFF if none */
+    uint32_t n_open_conns;        /* connections PREFIX */
+} uvhttp_ws_utf8_frames_summary_t;
+
+int uvhttp_ws_gpu_validate_utf8_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                        uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                        uint32_t max_frames, const uvhttp_ws_stream_t* d_streams,
+                                        const uvhttp_ws_stream_result_t* d_results, uint32_t n_streams,
+                                        const uvhttp_ws_utf8_state_t* d_state_in, uint32_t flags,
+                                        uvhttp_ws_utf8_conn_verdict_t* d_verdict,
+                                        uvhttp_ws_utf8_frames_summary_t* d_summary, void* stream);
+int uvhttp_ws_gpu_validate_utf8_inplace(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                        uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                        uint32_t n_frames,
+                                        const uvhttp_ws_batch_summary_t* d_batch_summary,
+                                        uint32_t flags, uvhttp_ws_utf8_conn_verdict_t* d_verdict,
+                                        uvhttp_ws_utf8_frames_summary_t* d_summary, void* stream);
+/* Host twin (plain C, host copies of the wire and descriptors): the same verdict for one
+ * connection, desc[first_frame, first_frame + n_delivered), with open_opcode the carried-in
+ * message's opcode (0 = none; a stream's pending_opcode when its pending_bytes != 0) and
+ * state_in its open sequence (NULL = zero; used only when open_opcode is TEXT).  What a
+ * pipeline user calls on wait()'s host copies, and the reference of "device == host".
+ * Returns 0, or -1 for NULL arguments (desc may be NULL when n_delivered is 0). */
+int uvhttp_ws_utf8_judge_frames(const uint8_t* wire, uint64_t wire_len,
+                                const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                                uint32_t n_delivered, int open_opcode,
+                                const uvhttp_ws_utf8_state_t* state_in, uint32_t flags,
+                                uvhttp_ws_utf8_conn_verdict_t* out);
+
 /* ---- batched send-side framing ---------------------------------------------------------- */
 /* One frame to build: uvhttp_ws_build_frame(ctx, buf, size, payload, len, opcode, mask, fin)
  * (src/uvhttp_websocket.c:204-285).  The reference draws a client's masking key from the

@@ -18,7 +18,15 @@ validation time has the decode step it would follow beside it: `vs_decode` = val
 
     python tools/bench_utf8.py [--steps K] [--warmup W] [--shapes c3,c4] [--scale S]
 
-One JSON line per (shape, content), then nothing else on stdout.
+--decode inplace | streams times the frame-level calls instead (uvhttp_ws_gpu_validate_utf8_inplace
+after decode_inplace with descriptors; _streams after decode_streams, C4 only: 4 096 connections
+x 256 frames).  The config's TEXT frames are generated on the device, decoded, and their
+payloads overwritten with the text (every frame its own message; for C4 also every message cut
+into 4 fragments, the mixed text's characters crossing the cuts).  `vs_decode` = validate / the
+same-run decode step of the same wire; for unfragmented runs the compact form's validator over
+the same payload ranges (generic form, the wire as its data) is timed beside it.
+
+One JSON line per (shape, content[, fragments]), then nothing else on stdout.
 """
 import argparse
 import json
@@ -72,18 +80,125 @@ def timed(torch, fn, steps, warmup):
     return ms[len(ms) // 2], ms[0], sum(ms) / len(ms)
 
 
+def frames_mode(args, t, U, eng, dev):
+    """--decode inplace | streams"""
+    for shape in args.shapes.split(","):
+        _, frames, plen, _, mm = SHAPES[shape]
+        if args.decode == "streams" and shape != "c4":
+            continue
+        per = 256  # frames per connection (streams)
+        frames = max(per, int(frames * args.scale)) // per * per
+        conns = frames // per if args.decode == "streams" else 1
+        stride = U.gen_frame_stride(plen)
+        hdr, wire_len = stride - plen, stride * frames
+        wire = t.empty(wire_len + 64, dtype=t.uint8, device=dev)
+        eng.gen_frames(wire, frames, plen, 0x5EED, opcode0=1, fragmented=False)
+        rows = wire[:wire_len].view(frames, stride)
+        desc, summ = eng.alloc_outputs(frames)
+        verdict = t.zeros(conns * 16, dtype=t.uint8, device=dev)
+        usum = t.zeros(16, dtype=t.uint8, device=dev)
+        if args.decode == "streams":
+            st = np.zeros(conns, dtype=U.STREAM_DT)
+            st["begin"] = np.arange(conns, dtype=np.uint64) * per * stride
+            st["len"] = per * stride
+            st["recv_buffer_size"] = max(65536, per * stride)
+            st["max_frame_size"], st["max_message_size"], st["is_server"] = 16 << 20, mm, 1
+            d_st = t.from_numpy(st.view(np.uint8).copy()).to(dev)
+            res = t.zeros(conns * 64, dtype=t.uint8, device=dev)
+            decode_name = "decode_streams"
+
+            def decode():
+                eng.decode_streams(wire, d_st, conns, frames, desc=desc, results=res, wire_len=wire_len)
+
+            def validate():
+                eng.validate_utf8_streams(wire, desc, frames, d_st, res, conns, verdict=verdict, summary=usum,
+                                          wire_len=wire_len)
+        else:
+            eng.reserve(frames, wire_len, 0)
+            decode_name = "decode_inplace"
+
+            def decode():
+                eng.decode_inplace(wire, frames, stride=stride, max_message_size=mm, wire_len=wire_len,
+                                   desc=desc, summary=summ)
+
+            def validate():
+                eng.validate_utf8_inplace(wire, desc, frames, summ, verdict=verdict, summary=usum, wire_len=wire_len)
+
+        table = np.zeros(frames, dtype=[("arena_off", "<u8"), ("len", "<u8"), ("first_frame", "<u4"),
+                                        ("last_frame", "<u4"), ("opcode", "<i4"), ("reserved", "<u4")])
+        table["arena_off"] = np.arange(frames, dtype=np.uint64) * stride + hdr
+        table["len"], table["opcode"] = plen, 1
+        d_table = t.from_numpy(table.view(np.uint8).copy()).to(dev)
+        cverdict = t.zeros(frames * 4, dtype=t.uint8, device=dev)
+        csum = t.zeros(16, dtype=t.uint8, device=dev)
+        for cut in ((1, 4) if shape == "c4" else (1,)):
+            # byte 0 of every header: FIN | TEXT, or TEXT, CONT, CONT, FIN | CONT
+            b0 = t.tensor([0x81] if cut == 1 else [0x01, 0x00, 0x00, 0x80], dtype=t.uint8, device=dev)
+            rows[:, 0] = b0.repeat(frames // cut)
+            d_med, d_lo, d_mean = timed(t, decode, args.steps, args.warmup)
+            if args.decode == "streams":
+                assert all(r.n_delivered == per and r.status == 0 for r in eng.read_stream_results(res, conns))
+            else:
+                assert eng.read_summary(summ)["n_delivered"] == frames
+            dec = {"ms": round(d_med, 4), "min_ms": round(d_lo, 4), "mean_ms": round(d_mean, 4),
+                   "payload_gibs": round(frames * plen / (d_med * 1e-3) / GIB, 1)}
+            for content in ("ascii", "mixed"):
+                if content == "ascii":
+                    tmp = t.empty(frames * plen, dtype=t.uint8, device=dev).random_(0x20, 0x7F)
+                    rows[:, hdr:] = tmp.view(frames, plen)
+                    del tmp
+                else:
+                    one = t.from_numpy(np.frombuffer(mixed_message(plen * cut), np.uint8).copy()).to(dev)
+                    rows.view(frames // cut, cut, stride)[:, :, hdr:] = one.view(1, cut, plen)
+                med, lo, mean = timed(t, validate, args.steps, args.warmup)
+                v = eng.read_utf8_conn_verdicts(verdict, conns)
+                assert all(x["status"] == U.UTF8_VALID and x["first_invalid"] == 0xFFFFFFFF for x in v), v[:2]
+                us = eng.read_utf8_frames_summary(usum)
+                assert us == {"n_text_frames": frames, "n_invalid_conns": 0, "first_invalid_conn": 0xFFFFFFFF,
+                              "n_open_conns": 0}, us
+                nbytes = frames * plen
+                line = {
+                    "metric": "UTF-8 validation GiB/s of text (device-resident, after %s)" % decode_name,
+                    "value": round(nbytes / (med * 1e-3) / GIB, 1), "unit": "GiB/s", "n_gpus": 1,
+                    "higher_is_better": True, "steps": args.steps, "warmup": args.warmup,
+                    "shape": shape, "decode": args.decode, "content": content, "fragments": cut,
+                    "config": {"frames": frames, "payload_bytes": plen, "connections": conns, "text_bytes": nbytes},
+                    "ms": round(med, 4), "min_ms": round(lo, 4), "mean_ms": round(mean, 4),
+                    "hbm_fraction_of_8TBs": round(nbytes / (med * 1e-3) / HBM_PEAK, 3),
+                    "same_run_decode": {decode_name: dec},
+                    "vs_decode": round(med / d_med, 3),
+                }
+                if cut == 1:
+                    c_med, c_lo, _ = timed(t, lambda: eng.validate_utf8(
+                        wire[:wire_len], d_table, frames, n_msgs=frames, verdict=cverdict, summary=csum),
+                        args.steps, args.warmup)
+                    cs = eng.read_utf8_summary(csum)
+                    assert cs["n_text"] == frames and cs["n_invalid"] == 0, cs
+                    line["same_run_compact_form"] = {"ms": round(c_med, 4), "min_ms": round(c_lo, 4),
+                                                     "gibs": round(nbytes / (c_med * 1e-3) / GIB, 1)}
+                print(json.dumps(line), flush=True)
+        del wire, rows, desc, d_table, cverdict
+        t.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shapes", default="c3,c4")
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the config's frames (smoke runs)")
+    ap.add_argument("--decode", choices=["compact", "inplace", "streams"], default="compact",
+                    help="which decode the validation follows (compact: the generic form over an arena)")
     args = ap.parse_args()
 
     import torch
     import uvhttp_amd as U
     t, dev = torch, "cuda:0"
     eng = U.GpuEngine(0)
+    if args.decode != "compact":
+        frames_mode(args, t, U, eng, dev)
+        eng.close()
+        return
     for shape in args.shapes.split(","):
         mlen, frames, plen, frag, mm = SHAPES[shape]
         frames = max(1, int(frames * args.scale))

@@ -93,6 +93,27 @@ class Utf8State(C.Structure):
 
 
 UTF8_VALID, UTF8_INVALID, UTF8_NOT_TEXT, UTF8_PREFIX, UTF8_BAD_RANGE = range(5)
+UTF8_CHECK_CLOSE = 0x1  # UVHTTP_WS_UTF8_CHECK_CLOSE
+
+
+class Utf8ConnVerdict(C.Structure):
+    """uvhttp_ws_utf8_conn_verdict_t (16 B)."""
+    _fields_ = [("first_invalid", C.c_uint32), ("n_text_frames", C.c_uint32), ("state", Utf8State),
+                ("status", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+    def as_dict(self):
+        return {"first_invalid": self.first_invalid, "n_text_frames": self.n_text_frames,
+                "state": (bytes(self.state.pend[: self.state.n]), self.state.n),
+                "status": self.status}
+
+
+class Utf8FramesSummary(C.Structure):
+    """uvhttp_ws_utf8_frames_summary_t (16 B)."""
+    _fields_ = [("n_text_frames", C.c_uint32), ("n_invalid_conns", C.c_uint32),
+                ("first_invalid_conn", C.c_uint32), ("n_open_conns", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Stream(C.Structure):
@@ -318,6 +339,12 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_ws_gpu_validate_utf8": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
         "uvhttp_ws_utf8_feed": (C.c_int, [C.POINTER(Utf8State), vp, C.c_size_t]),
         "uvhttp_ws_utf8_finish": (C.c_int, [C.POINTER(Utf8State)]),
+        "uvhttp_ws_gpu_validate_utf8_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, u32,
+                                                          vp, vp, vp]),
+        "uvhttp_ws_gpu_validate_utf8_inplace": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
+        "uvhttp_ws_utf8_judge_frames": (C.c_int, [vp, u64, vp, u32, u32, C.c_int,
+                                                  C.POINTER(Utf8State), u32,
+                                                  C.POINTER(Utf8ConnVerdict)]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -448,6 +475,23 @@ def utf8_feed(state: Utf8State, data) -> int:
 def utf8_finish(state: Utf8State) -> int:
     """uvhttp_ws_utf8_finish: 0 iff the message may end here (no sequence is open)."""
     return int(lib().uvhttp_ws_utf8_finish(C.byref(state)))
+
+
+def utf8_judge_frames(wire, desc, first_frame, n_delivered, open_opcode=0, state_in=None,
+                      flags=0, wire_len=None) -> dict:
+    """uvhttp_ws_utf8_judge_frames: the host twin of GpuEngine.validate_utf8_streams / _inplace
+    for one connection.  `wire` = host bytes of the decoded wire, `desc` = host bytes (or a numpy
+    array) of uvhttp_ws_frame_desc_t records -> Utf8ConnVerdict.as_dict()."""
+    wb = _host_buf(wire)
+    db = _host_buf(desc)
+    out = Utf8ConnVerdict()
+    n = len(wire) if wire_len is None else wire_len
+    rc = lib().uvhttp_ws_utf8_judge_frames(wb, n, db, first_frame, n_delivered, open_opcode,
+                                           C.byref(state_in) if state_in is not None else None,
+                                           flags, C.byref(out))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_utf8_judge_frames: bad argument")
+    return out.as_dict()
 
 
 class WsConnection:
@@ -752,6 +796,56 @@ class GpuEngine:
             C.c_void_p(verdict.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
             "validate_utf8")
         return verdict, summary
+
+    def _utf8_frames_out(self, n, verdict, summary):
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if verdict is None:
+            verdict = t.zeros(max(1, n) * C.sizeof(Utf8ConnVerdict), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(Utf8FramesSummary), dtype=t.uint8, device=dev)
+        return verdict, summary
+
+    def validate_utf8_streams(self, wire, desc, max_frames, streams_dev, results, n_streams,
+                              state_in=None, flags=0, verdict=None, summary=None, wire_len=None,
+                              stream=None):
+        """uvhttp_ws_gpu_validate_utf8_streams after decode_streams / decode_reads over the same
+        device tensors; state_in = device uint8 tensor of n_streams uvhttp_ws_utf8_state_t (the
+        previous call's verdict states) or None.  Returns (verdict, summary) device tensors:
+        n_streams 16-byte uvhttp_ws_utf8_conn_verdict_t and uvhttp_ws_utf8_frames_summary_t."""
+        verdict, summary = self._utf8_frames_out(n_streams, verdict, summary)
+        self._check(self._L.uvhttp_ws_gpu_validate_utf8_streams(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), max_frames, C.c_void_p(streams_dev.data_ptr()),
+            C.c_void_p(results.data_ptr()), n_streams,
+            C.c_void_p(state_in.data_ptr() if state_in is not None else None), flags,
+            C.c_void_p(verdict.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
+            "validate_utf8_streams")
+        return verdict, summary
+
+    def validate_utf8_inplace(self, wire, desc, n_frames, batch_summary, flags=0, verdict=None,
+                              summary=None, wire_len=None, stream=None):
+        """uvhttp_ws_gpu_validate_utf8_inplace after decode_inplace (with descriptors) over the
+        same device tensors.  Returns (verdict [1], summary) device tensors."""
+        verdict, summary = self._utf8_frames_out(1, verdict, summary)
+        self._check(self._L.uvhttp_ws_gpu_validate_utf8_inplace(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), n_frames, C.c_void_p(batch_summary.data_ptr()), flags,
+            C.c_void_p(verdict.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
+            "validate_utf8_inplace")
+        return verdict, summary
+
+    @staticmethod
+    def read_utf8_conn_verdicts(verdict, n):
+        """host copy of the first n connection verdicts -> [dict] (Utf8ConnVerdict.as_dict)"""
+        sz = C.sizeof(Utf8ConnVerdict)
+        raw = bytes(verdict[: n * sz].cpu().numpy().tobytes())
+        return [Utf8ConnVerdict.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_utf8_frames_summary(summary) -> dict:
+        raw = bytes(summary.cpu().numpy().tobytes())
+        return Utf8FramesSummary.from_buffer_copy(raw).as_dict()
 
     @staticmethod
     def read_utf8(verdict, n):

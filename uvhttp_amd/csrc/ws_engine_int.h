@@ -21,6 +21,10 @@ UVWS_INTERNAL int uvws_call_enter(uvhttp_ws_gpu_engine_t* e, hipStream_t s);
 UVWS_INTERNAL int uvws_call_leave(uvhttp_ws_gpu_engine_t* e, int prev_device, const char* what);
 // Sets last_error and returns `code`.
 UVWS_INTERNAL int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what);
+// The frame UTF-8 validator's engine-owned scratch of at least `bytes` (not zeroed), grown on
+// the call's stream like every other scratch block; null when it cannot grow (a captured call
+// that would allocate, or out of memory).  Call between uvws_call_enter and uvws_call_leave.
+UVWS_INTERNAL void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"
 

@@ -5623,6 +5623,8 @@ struct uvhttp_ws_gpu_engine {
     int sum_fast;              // summary-only stride decode in one payload pass (UVHTTP_WS_SUMMARY_FAST=0: off)
     uvhttp_ws_frame_desc_t* dscr;  // descriptor scratch for d_desc == NULL calls
     uint64_t dscr_cap;
+    void* u8_mem;              // the frame UTF-8 validator's scratch (utf8_gpu.hip; uvws_utf8_scratch)
+    uint64_t u8_bytes;
     uint32_t* ctl;             // device control words (kCtl*), own allocation
     uint32_t faults_seen;      // ctl[kCtlFaults] at the last engine_sync
     uint32_t max_polls;        // look-back wait bound (UVHTTP_WS_MAX_POLLS: tests)
@@ -5781,6 +5783,7 @@ void uvhttp_ws_gpu_engine_free(uvhttp_ws_gpu_engine_t* e) {
     scratch_free(e, e->wr_mem);
     scratch_free(e, e->dscr);
     scratch_free(e, e->sp_mem);
+    scratch_free(e, e->u8_mem);
     if (e->pool_ok) (void)hipStreamSynchronize(nullptr);
     if (e->ctl) (void)hipFree(e->ctl);
     if (e->stamp_mem) (void)hipFree(e->stamp_mem);
@@ -6296,6 +6299,19 @@ static uvhttp_ws_frame_desc_t* desc_scratch(uvhttp_ws_gpu_engine_t* e, uint32_t 
     }
     e->dscr_cap = want;
     return e->dscr;
+}
+
+// ws_engine_int.h: the frame UTF-8 validator's scratch, by the same rule
+void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
+    if (e->u8_mem && e->u8_bytes >= bytes) return e->u8_mem;
+    if (e->capturing) return nullptr;
+    e->u8_bytes = 0;
+    if (scratch_grow(e, &e->u8_mem, bytes, false, s, true) != hipSuccess) {
+        e->u8_mem = nullptr;
+        return nullptr;
+    }
+    e->u8_bytes = bytes;
+    return e->u8_mem;
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot

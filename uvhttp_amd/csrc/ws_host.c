@@ -663,3 +663,79 @@ int uvhttp_ws_utf8_feed(uvhttp_ws_utf8_state_t* st, const uint8_t* data, size_t 
 int uvhttp_ws_utf8_finish(const uvhttp_ws_utf8_state_t* st) {
     return (st != NULL && st->n == 0) ? 0 : -1;
 }
+
+/* One connection's delivered frames, walked in order (the host twin of
+ * uvhttp_ws_gpu_validate_utf8_streams / _inplace): the decoder's message membership, feed per
+ * TEXT frame, finish at FIN.  After the first INVALID / BAD_RANGE frame only the membership is
+ * still followed (n_text_frames counts every TEXT frame). */
+static int utf8_range_ok(uint64_t wire_len, uint64_t off, uint64_t len) {
+    return len <= wire_len && off <= wire_len - len;
+}
+
+int uvhttp_ws_utf8_judge_frames(const uint8_t* wire, uint64_t wire_len,
+                                const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                                uint32_t n_delivered, int open_opcode,
+                                const uvhttp_ws_utf8_state_t* state_in, uint32_t flags,
+                                uvhttp_ws_utf8_conn_verdict_t* out) {
+    if (out == NULL || (desc == NULL && n_delivered != 0) || (wire == NULL && wire_len != 0)) return -1;
+    memset(out, 0, sizeof(*out));
+    out->first_invalid = 0xFFFFFFFFu;
+    int op = (open_opcode == 1 || open_opcode == 2) ? open_opcode : 0;
+    uvhttp_ws_utf8_state_t st;
+    memset(&st, 0, sizeof(st));
+    if (op == 1 && state_in != NULL) {
+        st = *state_in;
+        if (st.n > 3) st.n = 3;
+    }
+    uint8_t status = UVHTTP_WS_UTF8_VALID;
+    for (uint32_t i = 0; i < n_delivered; ++i) {
+        const uvhttp_ws_frame_desc_t* d = &desc[(uint64_t)first_frame + i];
+        if (d->status != UVHTTP_WS_FRAME_OK) break; /* not delivered: the caller's count was wrong */
+        const int fop = d->opcode;
+        const int fin = (d->flags & UVHTTP_WS_FLAG_FIN) != 0;
+        const int judging = status == UVHTTP_WS_UTF8_VALID;
+        if (fop >= 8) {
+            if (fop == 8 && (flags & UVHTTP_WS_UTF8_CHECK_CLOSE) && d->payload_len > 2 && judging) {
+                if (!utf8_range_ok(wire_len, d->payload_off, d->payload_len)) {
+                    status = UVHTTP_WS_UTF8_BAD_RANGE;
+                } else {
+                    uvhttp_ws_utf8_state_t cs;
+                    memset(&cs, 0, sizeof(cs));
+                    if (uvhttp_ws_utf8_feed(&cs, wire + d->payload_off + 2, (size_t)(d->payload_len - 2)) != 0 ||
+                        uvhttp_ws_utf8_finish(&cs) != 0)
+                        status = UVHTTP_WS_UTF8_INVALID;
+                }
+                if (status != UVHTTP_WS_UTF8_VALID) out->first_invalid = first_frame + i;
+            }
+            continue;
+        }
+        if (fop == 1 || fop == 2) {
+            op = fop;
+            memset(&st, 0, sizeof(st));
+        } else if (fop != 0) {
+            continue; /* reserved opcodes are never delivered */
+        }
+        if (op == 1) {
+            out->n_text_frames++;
+            if (judging) {
+                if (!utf8_range_ok(wire_len, d->payload_off, d->payload_len))
+                    status = UVHTTP_WS_UTF8_BAD_RANGE;
+                else if (uvhttp_ws_utf8_feed(&st, d->payload_len ? wire + d->payload_off : NULL,
+                                             (size_t)d->payload_len) != 0 ||
+                         (fin && uvhttp_ws_utf8_finish(&st) != 0))
+                    status = UVHTTP_WS_UTF8_INVALID;
+                if (status != UVHTTP_WS_UTF8_VALID) out->first_invalid = first_frame + i;
+            }
+        }
+        if (fin) {
+            op = 0;
+            memset(&st, 0, sizeof(st));
+        }
+    }
+    if (status == UVHTTP_WS_UTF8_VALID && op == 1) {
+        status = UVHTTP_WS_UTF8_PREFIX;
+        out->state = st;
+    }
+    out->status = status;
+    return 0;
+}
