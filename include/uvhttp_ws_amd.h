@@ -402,7 +402,11 @@ int uvhttp_ws_gpu_stamp_simulate(uint64_t* ring, uint32_t epoch, uint32_t kind, 
  * every replay, so replays of the same graph over changing frame bytes never accept tags a
  * previous replay left behind.  Reserve the workspace before capturing (engine_reserve;
  * stream decode: one uncaptured call of the same or larger shape) — a captured call that
- * would allocate fails with EINVAL.  Kernel timing is not recorded inside a capture. */
+ * would allocate fails with EINVAL.  A graph holds the addresses of the engine's scratch as of
+ * its capture (among them every block the epoch kernel clears when the device epochs wrap),
+ * so make the engine's largest calls of every kind, or reserve, before capturing: a later
+ * uncaptured call that grows a scratch block invalidates the graphs captured before it.
+ * Kernel timing is not recorded inside a capture. */
 
 /* In-place decode: parse + validate every frame, run the fragment state machine, then
  * unmask the payload of every delivered frame in place in batch->wire (the reference

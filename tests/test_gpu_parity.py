@@ -592,15 +592,28 @@ def test_plan_frames_per_lane_identical(torch, fpt, monkeypatch):
         e.close()
 
 
-def test_epoch_wraparound(torch, monkeypatch):
-    """Decode calls on both sides of the epoch wrap (the workspace is cleared when the 30-bit
-    call tag runs out) decode like the oracle: big and small batches alternate so stale map
-    entries of an earlier call would show."""
+WRAP_BACK = 4  # test_epoch_wraparound starts this many calls before the host epochs' last
+
+
+def wrap_start():
+    """the UVHTTP_WS_EPOCH_START of test_epoch_wraparound, from the library's own limit (a
+    literal past it used to be replaced by 0, and the test ran at epochs 1 .. 16)"""
     import uvhttp_amd as U
-    monkeypatch.setenv("UVHTTP_WS_EPOCH_START", str((1 << 30) - 4))
+    return U.epoch_limits()[0] - WRAP_BACK
+
+
+def test_epoch_wraparound(torch, monkeypatch):
+    """Decode calls on both sides of the epoch wrap (the tagged scratch is cleared when the host's
+    half of the 30-bit call tag runs out) decode like the oracle: big and small batches alternate
+    so stale map entries of an earlier call would show.  The engine's epoch, read back after
+    every call, must fall once: the calls really crossed the wrap."""
+    import uvhttp_amd as U
+    monkeypatch.setenv("UVHTTP_WS_EPOCH_START", str(wrap_start()))
     e = U.GpuEngine(0)
     try:
+        assert e.epochs()[0] == wrap_start()
         rng = random.Random(31337)
+        seen = []
         for k in range(8):
             n = 3000 if k % 2 == 0 else 40
             sizes = [70000, 5000, 125] if k % 2 == 0 else [0, 3, 300]
@@ -609,6 +622,10 @@ def test_epoch_wraparound(torch, monkeypatch):
             for compact in (False, True):
                 ref, got = _run_both(torch, e, wire, n, offs=offs, mm=0, compact=compact)
                 _compare(ref, got, compact)
+                seen.append(e.epochs()[0])
+        falls = [i for i in range(1, len(seen)) if seen[i] < seen[i - 1]]
+        assert falls == [WRAP_BACK] and seen[WRAP_BACK - 1] == U.epoch_limits()[0] and \
+            seen[WRAP_BACK] == 1, seen
     finally:
         e.close()
 

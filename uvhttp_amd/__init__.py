@@ -283,7 +283,8 @@ EXPERIMENT_KNOBS = (
     "UVHTTP_WS_WALK", "UVHTTP_WS_TIME_CHAIN", "UVHTTP_WS_SPEC", "UVHTTP_WS_SPEC_MAX",
     "UVHTTP_WS_SUMMARY_FAST", "UVHTTP_WS_TILE", "UVHTTP_WS_TIMING_FENCE", "UVHTTP_WS_PIPE_IN_FLIGHT",
     "UVHTTP_TLS_CRYPT_GRID", "UVHTTP_WS_BATCHER_TRACE", "UVHTTP_WS_BATCHER_FAIL_EVERY",
-    "UVHTTP_WS_COPY_SSE2", "UVHTTP_WS_DESC_EMIT", "UVHTTP_WS_STREAM_SPEC")
+    "UVHTTP_WS_COPY_SSE2", "UVHTTP_WS_DESC_EMIT", "UVHTTP_WS_STREAM_SPEC",
+    "UVHTTP_WS_EPOCH_PERIOD", "UVHTTP_WS_DEV_EPOCH_START")
 
 
 def experiment_knobs_set():
@@ -433,7 +434,25 @@ def load_library(path: str) -> C.CDLL:
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
+    # test hooks only the experiment build exports (ws_gpu.hip, -DUVWS_EXPERIMENTS)
+    hooks = {
+        "uvhttp_ws_gpu_test_epoch_limits": (None, [C.POINTER(u32), C.POINTER(u32)]),
+        "uvhttp_ws_gpu_test_engine_epochs": (C.c_int, [vp, vp, C.POINTER(u32), C.POINTER(u32)]),
+    }
+    for name, (res, args) in hooks.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
     return L
+
+
+def epoch_limits():
+    """(kMaxHostEpoch, kMaxEpoch): the last epoch of the host's and of the device's half of the
+    decode calls' tag space (ws_gpu.hip).  From the experiment build; needs no GPU."""
+    mh, me = C.c_uint32(0), C.c_uint32(0)
+    test_hooks_library().uvhttp_ws_gpu_test_epoch_limits(C.byref(mh), C.byref(me))
+    return mh.value, me.value
 
 
 def gen_frame_stride(payload_len: int) -> int:
@@ -601,6 +620,9 @@ class GpuEngine:
         self.device = device
         h = C.c_void_p()
         rc = L.uvhttp_ws_gpu_engine_create(device, C.byref(h))
+        if rc == -1 and experiment_knobs_set():  # (EINVAL: the experiment build refused a value)
+            raise GpuError(f"uvhttp_ws_gpu_engine_create({device}) failed rc={rc}: an experiment "
+                           f"switch has a value out of range ({', '.join(experiment_knobs_set())})")
         if rc != 0:
             raise GpuError(f"uvhttp_ws_gpu_engine_create({device}) failed rc={rc} "
                            "(needs an MI355X / gfx950 and the HIP runtime)")
@@ -630,6 +652,17 @@ class GpuEngine:
     def reserve(self, max_frames, max_wire, max_arena=0):
         self._check(self._L.uvhttp_ws_gpu_engine_reserve(self.h, max_frames, max_wire,
                                                          max_arena), "reserve")
+
+    def epochs(self, stream=None):
+        """(host epoch, device epoch): the tag of the engine's latest uncaptured call and, once
+        `stream` has drained, of the latest replay of a captured one (0: none).  A test hook of
+        the experiment build, so that a wrap test can assert it crossed the wrap."""
+        if not hasattr(self._L, "uvhttp_ws_gpu_test_engine_epochs"):
+            raise GpuError("epochs(): only the experiment build has this test hook")
+        he, de = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.uvhttp_ws_gpu_test_engine_epochs(self.h, self._stream(stream),
+                                                             C.byref(he), C.byref(de)), "epochs")
+        return he.value, de.value
 
     def set_tile(self, block: int, vectors_per_lane: int):
         self._check(self._L.uvhttp_ws_gpu_engine_set_tile(self.h, block, vectors_per_lane),

@@ -20,6 +20,7 @@
 // no MFMA (nothing here is matrix-shaped).
 #include <hip/hip_runtime.h>
 
+#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -5546,19 +5547,27 @@ __global__ __launch_bounds__(kBlock) void k_gen_frames(uint8_t* wire, uint32_t f
 // k_epoch: first kernel of a captured call.  Every block reads the current device epoch,
 // then the last block to finish stores the next one (all reads happen before the store,
 // which waits for every block's done-increment).  When the device half of the epoch space is
-// used up the workspace and the send-side map are cleared first (grid-stride), so no stale
-// tag can match after the wrap.
-__global__ __launch_bounds__(kBlock) void k_epoch(uint32_t* ctl, uint64_t* ws_words,
-                                                  uint64_t n_ws, uint64_t* bs_words,
-                                                  uint64_t n_bs) {
+// used up every epoch-tagged allocation is cleared first (grid-stride): the workspace, the
+// send-side map, the speculative stream decode's scratch and the stream scratch, and the ctl
+// words that hold an epoch, so no stale tag can match or outrank a live one after the wrap
+// ("Epoch-tagged state").  The blocks are the engine's as of the capture, like
+// every other pointer a captured call holds.
+struct EpochClear {
+    uint64_t* p[4];  // ws_mem, bs_mem, sp_mem, ss_mem (null: not allocated)
+    uint64_t n[4];   // their sizes in 8-byte words
+};
+__global__ __launch_bounds__(kBlock) void k_epoch(uint32_t* ctl, EpochClear c) {
     const uint32_t e = *reinterpret_cast<volatile uint32_t*>(ctl + kCtlEpoch);
     const bool wrap = e >= kMaxEpoch || e <= kMaxHostEpoch;  // also the first captured call
     if (wrap) {
         const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-        for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < n_ws; k += stride)
-            ws_words[k] = 0;
-        for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < n_bs; k += stride)
-            bs_words[k] = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < c.n[m]; k += stride)
+                c.p[m][k] = 0;
+        // (no kernel of an earlier call still runs, and k_epoch itself reads none of these)
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            ctl[kCtlFaultEp] = ctl[kCtlGate] = ctl[kCtlSpecOff] = ctl[kCtlSpecBreak] = 0;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -5588,7 +5597,8 @@ struct uvhttp_ws_gpu_engine {
     int timing;                // 0: off; k >= 1: HIP events around every k-th call's payload kernel
     uint64_t timing_calls;     // calls seen while timing (the sampling counter)
     int tile_block, tile_vpt;  // payload kernel shape, 0 = automatic
-    uint32_t epoch;            // tag of the latest decode call, 1 .. kMaxEpoch
+    uint32_t epoch;            // tag of the latest host-issued call, 1 .. epoch_max
+    uint32_t epoch_max;        // host epochs wrap after this one: kMaxHostEpoch (tests: UVHTTP_WS_EPOCH_PERIOD)
     int plan_fpt;              // k_plan frames per lane, 0 = automatic
     int fused_off;             // UVHTTP_WS_FUSED=0: stride batches take the k_plan-first path
     uint64_t fused_max_avg;    // fused only up to this many wire bytes per frame (UVHTTP_WS_FUSED_MAX)
@@ -5597,6 +5607,7 @@ struct uvhttp_ws_gpu_engine {
     int walk_mode;             // stream frame discovery: 0 automatic, 1 lane, 2 wave
     void* ss_mem;              // stream-decode scratch
     uint32_t ss_frames, ss_reads;
+    size_t ss_bytes;
     StreamScratch ss;
     void* wt_mem;              // single-pass walk scratch (frame starts per connection slice)
     uint64_t wt_cap;
@@ -5611,6 +5622,7 @@ struct uvhttp_ws_gpu_engine {
     void* sp_mem;              // its scratch: SpecConn per connection, block counts, tile claims
     uint32_t sp_streams;
     uint64_t sp_tiles;
+    size_t sp_bytes;           // spec_layout(sp_streams, sp_tiles).bytes
     int spec_on;               // compact stride batches: the speculative pass (UVHTTP_WS_SPEC=0: off)
     uint64_t spec_max_avg;     // ... up to this many wire bytes per frame (UVHTTP_WS_SPEC_MAX)
     int time_chain;            // UVHTTP_WS_TIME_CHAIN=1: stream decode timing brackets the whole
@@ -5678,15 +5690,43 @@ uint64_t uvhttp_ws_gen_frame_stride(uint64_t payload_len) {
 // (look-back give-up, epoch wrap).  The product library reads no environment (VERDICT r05
 // item 9).  Every variant reachable here takes block tickets where it waits on other blocks
 // and gives the product's results (tests/ run them against the oracle).
-static void experiment_knobs(uvhttp_ws_gpu_engine_t* e) {
+// an epoch knob's value: a whole number in lo .. hi, or the engine is not created (a value that
+// was silently replaced made a wrap test run nowhere near the wrap)
+static bool epoch_knob(const char* name, uint64_t lo, uint64_t hi, bool* set, uint32_t* out) {
+    *set = false;
+    const char* s = getenv(name);
+    if (!s) return true;
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long v = strtoull(s, &end, 0);
+    if (errno || end == s || *end || *s == '-' || v < lo || v > hi) {
+        fprintf(stderr, "uvhttp_ws_amd: %s=%s is outside %llu .. %llu\n", name, s,
+                (unsigned long long)lo, (unsigned long long)hi);
+        return false;
+    }
+    *set = true;
+    *out = (uint32_t)v;
+    return true;
+}
+
+// false: a knob's value is out of range (engine_create fails with EINVAL)
+static bool experiment_knobs(uvhttp_ws_gpu_engine_t* e, uint32_t* dev_epoch_start) {
     if (const char* mp = getenv("UVHTTP_WS_MAX_POLLS")) e->max_polls = (uint32_t)strtoul(mp, nullptr, 0);
     if (const char* po = getenv("UVHTTP_WS_SCRATCH_POOL")) e->pool_ok &= atoi(po) != 0;
     if (const char* fp = getenv("UVHTTP_WS_PLAN_FPT")) e->plan_fpt = atoi(fp);
-    // start near the end of the epoch space to exercise the wrap-around clear
-    if (const char* ep = getenv("UVHTTP_WS_EPOCH_START")) {
-        const unsigned long v = strtoul(ep, nullptr, 0);
-        e->epoch = v < kMaxHostEpoch ? (uint32_t)v : 0;
-    }
+    // The epoch wrap (tests/test_gpu_epoch_wrap.py).  UVHTTP_WS_EPOCH_PERIOD=N: host epochs run
+    // 1 .. N, so a full cycle — a stale tag meeting its own epoch value again — takes N calls.
+    // UVHTTP_WS_EPOCH_START=v: the engine's latest epoch is v, the first call takes v + 1 (or
+    // wraps, v = the period's last).  UVHTTP_WS_DEV_EPOCH_START=v: ctl[kCtlEpoch] = v, so the
+    // first replay of a captured call takes v + 1 (or wraps, v = kMaxEpoch).
+    bool set;
+    uint32_t v = 0;
+    if (!epoch_knob("UVHTTP_WS_EPOCH_PERIOD", 2, kMaxHostEpoch, &set, &v)) return false;
+    if (set) e->epoch_max = v;
+    if (!epoch_knob("UVHTTP_WS_EPOCH_START", 0, e->epoch_max - 1, &set, &v)) return false;
+    if (set) e->epoch = v;
+    if (!epoch_knob("UVHTTP_WS_DEV_EPOCH_START", (uint64_t)kMaxHostEpoch + 1, kMaxEpoch, &set, &v)) return false;
+    *dev_epoch_start = set ? v : 0;
     if (const char* bs = getenv("UVHTTP_WS_BUILD_SMALL")) e->build_small = atoi(bs);
     if (const char* fu = getenv("UVHTTP_WS_FUSED")) e->fused_off = atoi(fu) == 0;
     if (const char* fm = getenv("UVHTTP_WS_FUSED_MAX")) e->fused_max_avg = strtoull(fm, nullptr, 10);
@@ -5711,6 +5751,7 @@ static void experiment_knobs(uvhttp_ws_gpu_engine_t* e) {
         int tb = 0, tv = 0;
         if (sscanf(tl, "%dx%d", &tb, &tv) == 2) (void)uvhttp_ws_gpu_engine_set_tile(e, tb, tv);  // (validated)
     }
+    return true;
 }
 #endif
 
@@ -5728,6 +5769,7 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     e->device = device;
     // the product configuration (each choice measured: DESIGN.md §4-5)
     e->max_polls = kMaxPolls;
+    e->epoch_max = kMaxHostEpoch;
     e->fused_max_avg = kFusedMaxAvg;
     // the fused path scans its records with k_plan's look-back (C4: 133-136 us per step against
     // 144-145 for reduce-then-scan, profiles/r03p6_*)
@@ -5764,7 +5806,23 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
         e->pool_ok = pools ? 1 : 0;
     }
 #ifdef UVWS_EXPERIMENTS
-    experiment_knobs(e);
+    {
+        uint32_t dev_start = 0;
+        bool ok = experiment_knobs(e, &dev_start);
+        if (ok && dev_start) {  // (a test's seed of the device epoch)
+            int prev = 0;
+            (void)hipGetDevice(&prev);
+            (void)hipSetDevice(device);
+            ok = hipMemcpy(e->ctl + kCtlEpoch, &dev_start, sizeof(dev_start), hipMemcpyHostToDevice) == hipSuccess &&
+                 hipDeviceSynchronize() == hipSuccess;
+            (void)hipSetDevice(prev);
+        }
+        if (!ok) {
+            (void)hipFree(e->ctl);
+            free(e);
+            return UVHTTP_WS_GPU_EINVAL;
+        }
+    }
 #endif
     *out = e;
     return UVHTTP_WS_GPU_OK;
@@ -5817,6 +5875,33 @@ int uvhttp_ws_gpu_engine_sync(uvhttp_ws_gpu_engine_t* e, void* stream) {
     }
     return UVHTTP_WS_GPU_OK;
 }
+
+#ifdef UVWS_EXPERIMENTS
+// Test hooks of the experiment build (not in include/: the product library has neither).
+// The ends of the two halves of the epoch space; host only, no device needed.
+void uvhttp_ws_gpu_test_epoch_limits(uint32_t* max_host_epoch, uint32_t* max_epoch) {
+    if (max_host_epoch) *max_host_epoch = kMaxHostEpoch;
+    if (max_epoch) *max_epoch = kMaxEpoch;
+}
+
+// The engine's latest host epoch and, once `stream` has drained, the device epoch
+// ctl[kCtlEpoch] (the one the latest replay of a captured call ran with; 0: none yet), so a
+// test can assert that its calls really crossed a wrap.
+int uvhttp_ws_gpu_test_engine_epochs(uvhttp_ws_gpu_engine_t* e, void* stream, uint32_t* host_epoch,
+                                     uint32_t* device_epoch) {
+    if (!e || !host_epoch || !device_epoch) return UVHTTP_WS_GPU_EINVAL;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (prev != e->device) (void)hipSetDevice(e->device);
+    hipError_t h = hipStreamSynchronize((hipStream_t)stream);
+    if (h == hipSuccess)
+        h = hipMemcpy(device_epoch, e->ctl + kCtlEpoch, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (prev != e->device) (void)hipSetDevice(prev);
+    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "epochs", h);
+    *host_epoch = e->epoch;
+    return UVHTTP_WS_GPU_OK;
+}
+#endif
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -6144,20 +6229,37 @@ static void timing_end(uvhttp_ws_gpu_engine_t* e, int k, hipStream_t s) {
     e->ev_used = k + 1;
 }
 
-// Record tags hold the epoch in 30 bits.  When the epoch space is used up the workspace is
-// cleared on the call's stream (once per 2^30 - 1 calls), so no entry left by an earlier call
-// can carry a live tag.
+// Record tags hold the epoch in 30 bits.  When the host's or the device's half of the epoch
+// space is used up (once per 2^29 - 1 calls), every epoch-tagged allocation is cleared on the
+// call's stream before the first epoch is issued again, so no entry left by an earlier call can
+// match a live tag (the == compared ones) or outrank a live claim (the max-claimed ones).  The
+// tagged items, block by block: DESIGN.md, "Epoch-tagged state".  Every block is a multiple of
+// 8 bytes (256-byte aligned sizes; BuildRec is 64 bytes).
+static EpochClear epoch_blocks(const uvhttp_ws_gpu_engine_t* e) {
+    EpochClear c;
+    c.p[0] = (uint64_t*)e->ws_mem, c.n[0] = e->ws_mem ? e->ws_bytes / 8 : 0;
+    c.p[1] = (uint64_t*)e->bs_mem, c.n[1] = e->bs_mem ? e->bs_tiles * sizeof(BuildRec) / 8 : 0;
+    c.p[2] = (uint64_t*)e->sp_mem, c.n[2] = e->sp_mem ? e->sp_bytes / 8 : 0;
+    c.p[3] = (uint64_t*)e->ss_mem, c.n[3] = e->ss_mem ? e->ss_bytes / 8 : 0;
+    return c;
+}
 
 static uint32_t next_epoch(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
     if (e->capturing) {  // the replay's k_epoch issues it; kernels read ctl[kCtlEpoch]
-        hipLaunchKernelGGL(k_epoch, dim3(64), dim3(kBlock), 0, s, e->ctl, (uint64_t*)e->ws_mem,
-                           (uint64_t)(e->ws_mem ? e->ws_bytes / 8 : 0), (uint64_t*)e->bs_mem,
-                           (uint64_t)(e->bs_mem ? e->bs_tiles * sizeof(BuildRec) / 8 : 0));
+        hipLaunchKernelGGL(k_epoch, dim3(64), dim3(kBlock), 0, s, e->ctl, epoch_blocks(e));
         return 0;
     }
-    if (e->epoch >= kMaxHostEpoch) {
-        (void)hipMemsetAsync(e->ws_mem, 0, e->ws_bytes, s);
-        if (e->bs_mem) (void)hipMemsetAsync(e->bs_mem, 0, e->bs_tiles * sizeof(BuildRec), s);
+    if (e->epoch >= e->epoch_max) {
+        // (the call's scratch is reserved before its epoch is taken, except the speculative
+        // stream scratch, which a call that grows it zeroes itself)
+        const EpochClear c = epoch_blocks(e);
+        for (int m = 0; m < 4; ++m)
+            if (c.n[m]) (void)hipMemsetAsync(c.p[m], 0, c.n[m] * 8, s);
+        // the ctl words that hold an epoch: kCtlFaultEp, then kCtlGate .. kCtlSpecBreak (not the
+        // device epoch, its counter or the fault count between them)
+        static_assert(kCtlGate + 1 == kCtlSpecOff && kCtlSpecOff + 1 == kCtlSpecBreak, "one run of words");
+        (void)hipMemsetAsync(e->ctl + kCtlFaultEp, 0, sizeof(uint32_t), s);
+        (void)hipMemsetAsync(e->ctl + kCtlGate, 0, 3 * sizeof(uint32_t), s);
         e->epoch = 0;
     }
     return ++e->epoch;
@@ -6684,8 +6786,10 @@ static int reserve_streams(uvhttp_ws_gpu_engine_t* e, uint32_t frames, uint32_t 
     if (h != hipSuccess) {
         e->ss_mem = nullptr;
         e->ss_frames = e->ss_reads = 0;
+        e->ss_bytes = 0;
         return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc stream scratch", h);
     }
+    e->ss_bytes = bytes;
     char* b = (char*)e->ss_mem;
     e->ss.frame_off = (uint64_t*)(b + o_off);
     e->ss.n_total = (uint32_t*)(b + o_tot);
@@ -6738,10 +6842,12 @@ static int reserve_spec(uvhttp_ws_gpu_engine_t* e, uint32_t streams, uint64_t ti
         e->sp_mem = nullptr;
         e->sp_streams = 0;
         e->sp_tiles = 0;
+        e->sp_bytes = 0;
         return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc speculative stream scratch", h);
     }
     e->sp_streams = ns;
     e->sp_tiles = nt;
+    e->sp_bytes = bytes;
     return UVHTTP_WS_GPU_OK;
 }
 
