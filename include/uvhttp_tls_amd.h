@@ -92,6 +92,7 @@ extern "C" {
 #define UVHTTP_TLS_REC_ERR_CAPACITY (-6)  /* records / layout exceed records[] or out_cap */
 #define UVHTTP_TLS_REC_ERR_KEY (-7)       /* key slot out of range, or key_len / version / cipher invalid
                                              (connection result only; no record counted) */
+#define UVHTTP_TLS_REC_ERR_RANGE (-8)     /* a send's frames lie outside frame_off[] / frames[] */
 
 /* AEAD of a key slot (uvhttp_tls_key_t.cipher). */
 #define UVHTTP_TLS_CIPHER_AES_GCM 0u            /* AES-128/256-GCM (key_len 16 / 32) */
@@ -158,6 +159,46 @@ typedef struct {
     uint8_t reserved;
 } uvhttp_tls_seal_t;
 
+/* One send: frames [first_frame, first_frame + n_frames) of a build_frames output, to one
+ * connection direction (32 bytes). */
+typedef struct {
+    uint64_t seq;          /* write sequence number of the send's first record */
+    uint32_t first_frame;
+    uint32_t n_frames;
+    uint32_t key;          /* key slot */
+    uint8_t type;          /* content type (23) */
+    uint8_t reserved[3];
+    uint64_t reserved2;
+} uvhttp_tls_send_t;
+
+/* One send's result (device-written, 48 bytes). */
+typedef struct {
+    uint64_t out_off;       /* start of the send's records in out */
+    uint64_t out_len;       /* bytes of its records: what one uv_write sends */
+    uint64_t next_seq;      /* seq + n_records */
+    uint32_t first_record;  /* index in records[] */
+    uint32_t n_records;
+    int32_t status;         /* 0, UVHTTP_TLS_REC_ERR_KEY / _RANGE / _CAPACITY */
+    uint32_t reserved;
+    uint64_t plain_len;     /* frame bytes sealed */
+} uvhttp_tls_send_result_t;
+
+/* Totals of one seal_frames call (device-written, 32 bytes). */
+typedef struct {
+    uint64_t out_bytes;  /* bytes of out the call needs */
+    uint32_t n_records;  /* records the call needs (saturates at 2^32 - 1) */
+    uint32_t n_failed;   /* sends whose status is not 0 */
+    uint64_t reserved[2];
+} uvhttp_tls_send_summary_t;
+
+#ifdef __cplusplus
+static_assert(sizeof(uvhttp_tls_send_t) == 32 && sizeof(uvhttp_tls_send_result_t) == 48 &&
+              sizeof(uvhttp_tls_send_summary_t) == 32, "send-side struct sizes");
+#else
+_Static_assert(sizeof(uvhttp_tls_send_t) == 32 && sizeof(uvhttp_tls_send_result_t) == 48 &&
+               sizeof(uvhttp_tls_send_summary_t) == 32, "send-side struct sizes");
+#endif
+
 typedef struct uvhttp_tls_gpu_engine uvhttp_tls_gpu_engine_t;
 
 /* UVHTTP_TLS_GPU_ENODEV without a gfx950 device (there is no CPU fallback). */
@@ -206,6 +247,62 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* eng, const uint8_t* src
                                 uint64_t src_len, const uvhttp_tls_seal_t* recs,
                                 uint32_t n_records, const uvhttp_tls_key_t* keys,
                                 uint32_t n_keys, uint8_t* out, uint64_t out_cap, void* stream);
+
+/* Seal built WebSocket frames into the TLS records of many connections: the hand-off
+ * uvhttp_ws_gpu_build_frames -> sealed records, the mirror of uvhttp_tls_gpu_ws_streams.  What it
+ * replaces: on a TLS connection uvhttp_ws_send_frame (src/uvhttp_websocket.c:543-575) hands every
+ * built frame to mbedtls_ssl_write in a loop, one record of at most 16 384 content bytes per
+ * call.  Here `frames` / `frame_off` are build_frames' d_out / d_out_off (n_frames_total + 1
+ * offsets) as they lie on the device, and a send names a run of those frames, a key slot and the
+ * write sequence number of its first record; the record plan is made on the device, so nothing
+ * is read back between the two calls.  All pointers are device pointers; the call is
+ * asynchronous on `stream` and does not synchronise with the host.
+ *
+ * Cutting.  Frame f has F = frame_off[f + 1] - frame_off[f] bytes and is cut on its own, as the
+ * mbedtls_ssl_write loop cuts it: ceil(F / max_fragment) records, every one of max_fragment
+ * content bytes except the last; a record never holds bytes of two frames; F = 0 gives no
+ * record.  max_fragment is 1..16384 (0 = 16384).
+ *
+ * Numbering and layout.  A send's records are numbered seq, seq + 1, ... across its frames in
+ * order.  Records lie back to back in out, sends in index order and a send's records in order,
+ * so out[out_off, out_off + out_len) of a send is one contiguous write.  The bytes of a record
+ * are exactly uvhttp_tls_gpu_seal_records' for the same (key, seq, type, content).  records[]
+ * receives one uvhttp_tls_seal_t per record (src_off into frames, out_off, seq, plain_len, key,
+ * type), send s's at [first_record, first_record + n_records); after the call it is a valid
+ * input to uvhttp_tls_gpu_seal_records (src = frames).
+ *
+ * Broadcast.  Sends may name the same or overlapping frame ranges: one built frame, N sends with
+ * N keys.  Sends are independent; two sends with the same key slot get the sequence numbers the
+ * caller gave them.
+ *
+ * Per-send failures (status set, 0 records, out_len 0, next_seq = seq; the other sends are not
+ * affected), checked in this order:
+ *   ERR_KEY    the key slot is >= n_keys, the slot's key is invalid, or the slot is above 65 535
+ *              (uvhttp_tls_seal_t carries a 16-bit slot);
+ *   ERR_RANGE  first_frame + n_frames > n_frames_total, or a frame of the send has frame_off[f] >
+ *              frame_off[f + 1] or frame_off[f + 1] > frames_len.  With frames_len = the out_cap
+ *              build_frames was given, this also catches every send that reaches into what a
+ *              build_frames wrote nothing of because that out_cap was too small.
+ * A failed send's out_off and first_record are where its records would have begun.  A send with
+ * n_frames = 0 (and first_frame <= n_frames_total) succeeds with no record.
+ *
+ * Capacity.  If the records of the sends without an error of their own exceed max_records, or
+ * their bytes exceed out_cap, every such send reports ERR_CAPACITY, every result has out_off,
+ * out_len, first_record, n_records and plain_len 0, nothing is written to out or records, and
+ * summary still holds the totals needed, so the caller can size and call again.  n_failed is
+ * then n_sends.
+ *
+ * Returns EINVAL for a null pointer with a non-zero count (summary is always required), for
+ * max_fragment > 16384, and for more than 2^26 sends, 2^28 frames or 2^28 records; ENODEV
+ * for a null engine where there is no device.  n_sends = 0 returns OK with a zeroed summary. */
+int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* eng, const uint8_t* frames,
+                               uint64_t frames_len, const uint64_t* frame_off,
+                               uint32_t n_frames_total, const uvhttp_tls_send_t* sends,
+                               uint32_t n_sends, const uvhttp_tls_key_t* keys, uint32_t n_keys,
+                               uint32_t max_fragment, uvhttp_tls_seal_t* records,
+                               uint32_t max_records, uvhttp_tls_send_result_t* results,
+                               uvhttp_tls_send_summary_t* summary, uint8_t* out, uint64_t out_cap,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,17 @@ plaintext is one masked BINARY WebSocket frame filling its records (65 528-byte 
 default 4 x 16 KiB), and a step is open_records -> ws_streams (one process_data call per
 record) -> decode_reads: ciphertext in HBM -> unmasked messages in HBM.  The rate is WebSocket
 payload bytes per second.
+
+--send: the send side.  `--conns` sends of `--frames` server (unmasked) BINARY frames of `--fsize`
+bytes each (header included), or with --broadcast `--conns` sends that all name one frame.  Three
+things are timed with device events in the same run, alternating: uvhttp_ws_gpu_build_frames +
+uvhttp_tls_gpu_seal_frames (the send path), the uvhttp_tls_gpu_seal_frames call alone, and
+uvhttp_tls_gpu_seal_records over the very record table seal_frames wrote (the crypto with a
+host-made plan: what the device-side plan is compared against).  The two outputs are compared
+byte for byte.  One JSON line, appended to --out (default profiles/tls_send_bench.jsonl).
+
+    python tools/bench_tls.py --send [--broadcast] [--conns N] [--frames F] [--fsize B]
+                              [--max-fragment M] [--version 13|12] [--klen 16|32] [--cipher aes|chacha]
 """
 import argparse
 import ctypes as C
@@ -93,6 +104,137 @@ def openssl_baseline(keyrec, seq, wire, n_rec, rlen, version, seconds, chacha=Fa
             "sample": f"{n_rec} records x {rlen} B, {el:.1f} s"}
 
 
+def frame_payload(fsize):
+    """payload length of the unmasked frame of fsize bytes (header 2 / 4 / 10)"""
+    for hdr, lo, hi in ((2, 0, 125), (4, 126, 65535), (10, 65536, 1 << 62)):
+        if lo <= fsize - hdr <= hi:
+            return fsize - hdr
+    raise SystemExit(f"no frame is {fsize} bytes long")
+
+
+def send_bench(args):
+    import torch as t
+    import _oracle as O  # test infrastructure: the key struct layout only
+    import uvhttp_amd as U
+
+    dev = "cuda:0"
+    ver = 0x0304 if args.version == 13 else 0x0303
+    chacha = args.cipher == "chacha"
+    n_sends = args.conns
+    per = 1 if args.broadcast else args.frames
+    n_frames = 1 if args.broadcast else n_sends * per
+    fsize, mf = args.fsize, args.max_fragment or 16384
+    plen = frame_payload(fsize)
+    rng = np.random.default_rng(7)
+    nk = min(n_sends, 65536)  # the record table's slot is 16-bit: send i uses slot i % 65 536
+    keys = np.zeros(nk, O.TLS_KEY_DT)
+    keys["key"] = rng.integers(0, 256, (nk, 32), dtype=np.uint8)
+    keys["iv"] = rng.integers(0, 256, (nk, 12), dtype=np.uint8)
+    keys["key_len"], keys["version"] = (32 if chacha else args.klen), ver
+    keys["cipher"] = O.CHACHA if chacha else O.AES_GCM
+    over = 5 + 16 + (1 if ver == 0x0304 else 0 if chacha else 8)
+    rec_per_frame = (fsize + mf - 1) // mf
+    n_rec = n_sends * per * rec_per_frame
+    out_bytes = n_sends * per * (fsize + rec_per_frame * over)
+    # build descriptors: payloads from a shared 64 MiB (or smaller) random source
+    src_len = max(plen, min(64 << 20, max(1, n_frames * plen)))
+    src = t.randint(0, 256, (src_len,), dtype=t.uint8, device=dev)
+    bd = np.zeros(n_frames, np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("key", "<u4"),
+                                      ("opcode", "u1"), ("fin", "u1"), ("mask", "u1"), ("r0", "u1"),
+                                      ("r1", "<u8")]))
+    bd["payload_off"] = (np.arange(n_frames, dtype=np.uint64) * np.uint64(plen)) % np.uint64(max(1, src_len - plen + 1))
+    bd["payload_len"], bd["opcode"], bd["fin"] = plen, 2, 1
+    sends = np.zeros(n_sends, np.dtype([("seq", "<u8"), ("first_frame", "<u4"), ("n_frames", "<u4"),
+                                        ("key", "<u4"), ("type", "u1"), ("r", "u1", 3), ("r2", "<u8")]))
+    sends["seq"] = rng.integers(0, 1 << 40, n_sends, dtype=np.uint64)
+    sends["first_frame"] = 0 if args.broadcast else np.arange(n_sends, dtype=np.uint64) * per
+    sends["n_frames"], sends["type"] = per, 23
+    sends["key"] = np.arange(n_sends) % nk
+    up = lambda a: t.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
+    d_bd, d_sends, d_keys = up(bd), up(sends), up(keys)
+    frames = t.empty(n_frames * fsize, dtype=t.uint8, device=dev)
+    d_off = t.zeros(n_frames + 1, dtype=t.int64, device=dev)
+    out = t.empty(out_bytes, dtype=t.uint8, device=dev)
+    out2 = t.empty(out_bytes, dtype=t.uint8, device=dev)
+    recs = t.zeros(n_rec * U.TLS_SEAL_BYTES, dtype=t.uint8, device=dev)
+    res = t.zeros(n_sends * U.TLS_SEND_RESULT_BYTES, dtype=t.uint8, device=dev)
+    summ = t.zeros(U.TLS_SEND_SUMMARY_BYTES, dtype=t.uint8, device=dev)
+    weng = U.GpuEngine(0)
+    eng = U.TlsEngine(0, library=U.load_library(args.lib) if args.lib else None)
+
+    def build():
+        weng.build_frames(src, d_bd, n_frames, frames, out_off=d_off)
+
+    def seal_frames():
+        eng.seal_frames(frames, d_off, n_frames, d_sends, n_sends, d_keys, nk, n_rec, out,
+                        max_fragment=args.max_fragment, records=recs, results=res, summary=summ)
+
+    def seal_records():
+        eng.seal_records(frames, recs, n_rec, d_keys, nk, out2)
+
+    def send_path():
+        build()
+        seal_frames()
+
+    legs = {"build_frames+seal_frames": send_path, "seal_frames": seal_frames,
+            "seal_records(same table)": seal_records}
+    for _ in range(max(1, args.warmup)):
+        for f in legs.values():
+            f()
+    t.cuda.synchronize()
+    sm = summ.cpu().numpy()
+    got_bytes, got_rec, got_failed = int(sm[:8].view("<u8")[0]), int(sm[8:12].view("<u4")[0]), int(sm[12:16].view("<u4")[0])
+    assert (got_bytes, got_rec, got_failed) == (out_bytes, n_rec, 0), (got_bytes, got_rec, got_failed)
+    assert t.equal(out, out2), "seal_frames and seal_records over its table differ"
+    times = {k: [] for k in legs}
+    for _ in range(args.steps):
+        for k, f in legs.items():  # alternating: the legs share whatever else the machine does
+            e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1))
+    # the seal kernels alone (engine HIP events), inside either call
+    eng.set_timing(True)
+    kern = {}
+    for k in ("seal_frames", "seal_records(same table)"):
+        eng.kernel_time()
+        for _ in range(3):
+            legs[k]()
+        t.cuda.synchronize()
+        ms, launches = eng.kernel_time()
+        kern[k] = round(ms / max(1, launches), 4)
+    eng.set_timing(False)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    plain = n_sends * per * fsize
+    aead = "ChaCha20-Poly1305" if chacha else f"AES-{args.klen * 8}-GCM"
+    shape = (f"broadcast of one {fsize}-byte frame to {n_sends} connections" if args.broadcast else
+             f"{n_sends} sends x {per} frame(s) of {fsize} bytes")
+    line = {
+        "metric": "TLS send path: built frames -> sealed records (device-resident)",
+        "value": round(plain / (med["seal_frames"] * 1e-3) / GIB, 2), "unit": "GiB/s of frame bytes (seal_frames)",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
+        "config": {"workload": f"{shape}, TLS 1.{args.version % 10} {aead}, max_fragment {mf}",
+                   "sends": n_sends, "frames": n_frames, "records": n_rec, "frame_bytes": fsize,
+                   "out_bytes": out_bytes, "broadcast": bool(args.broadcast)},
+        "ms_median": {k: round(v, 4) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 4) for k, v in times.items()},
+        "ms_max": {k: round(max(v), 4) for k, v in times.items()},
+        "seal_kernels_ms": kern,
+        "seal_frames_over_seal_records": round(med["seal_frames"] / med["seal_records(same table)"], 4),
+        "timing": "device events around each call, legs alternating within a step, medians",
+    }
+    if args.lib:
+        line["lib"] = os.path.basename(args.lib)
+    text = json.dumps(line)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conns", type=int, default=65536)
@@ -107,7 +249,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lib", default=None, help="another build of the library (A/B runs)")
     ap.add_argument("--chain", action="store_true", help="open_records -> ws_streams -> decode_reads")
+    ap.add_argument("--send", action="store_true", help="build_frames -> seal_frames beside seal_records")
+    ap.add_argument("--broadcast", action="store_true", help="--send: one frame, --conns sends")
+    ap.add_argument("--frames", type=int, default=1, help="--send: frames per send")
+    ap.add_argument("--fsize", type=int, default=65536, help="--send: bytes of a frame, header included")
+    ap.add_argument("--max-fragment", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "tls_send_bench.jsonl"),
+                    help="--send: the JSON line is appended here ('' = stdout only)")
     args = ap.parse_args()
+    if args.send:
+        return send_bench(args)
 
     import torch
     import _oracle as O  # test infrastructure: key structs and the CPU baseline leg only

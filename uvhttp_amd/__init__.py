@@ -426,6 +426,8 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_tls_gpu_open_records": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, vp,
                                                   u64, vp]),
         "uvhttp_tls_gpu_seal_records": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, u64, vp]),
+        "uvhttp_tls_gpu_seal_frames": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, u32, u32, vp,
+                                                 u32, vp, vp, vp, u64, vp]),
         "uvhttp_tls_gpu_ws_streams": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
@@ -1022,6 +1024,7 @@ class GpuPipeline:
 # ---- TLS record layer (include/uvhttp_tls_amd.h) -----------------------------------------
 
 TLS_RECORD_BYTES, TLS_RESULT_BYTES = 32, 64
+TLS_SEAL_BYTES, TLS_SEND_BYTES, TLS_SEND_RESULT_BYTES, TLS_SEND_SUMMARY_BYTES = 32, 32, 48, 32
 
 
 class TlsEngine:
@@ -1102,6 +1105,27 @@ class TlsEngine:
             self.h, C.c_void_p(src.data_ptr()), src.numel(), C.c_void_p(recs.data_ptr()),
             n_records, C.c_void_p(keys.data_ptr()), n_keys, C.c_void_p(out.data_ptr()),
             out.numel(), self._stream(stream)), "seal_records")
+
+    def seal_frames(self, frames, frame_off, n_frames_total, sends, n_sends, keys, n_keys,
+                    max_records, out, max_fragment=0, records=None, results=None, summary=None,
+                    frames_len=None, stream=None):
+        """uvhttp_tls_gpu_seal_frames: frames / frame_off are build_frames' out / out_off, sends
+        a device tensor of uvhttp_tls_send_t -> (records, results, summary) device tensors"""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if records is None:
+            records = t.zeros(max(1, max_records) * TLS_SEAL_BYTES, dtype=t.uint8, device=dev)
+        if results is None:
+            results = t.zeros(max(1, n_sends) * TLS_SEND_RESULT_BYTES, dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(TLS_SEND_SUMMARY_BYTES, dtype=t.uint8, device=dev)
+        self._check(self._L.uvhttp_tls_gpu_seal_frames(
+            self.h, C.c_void_p(frames.data_ptr()), frames.numel() if frames_len is None else frames_len,
+            C.c_void_p(frame_off.data_ptr()), n_frames_total, C.c_void_p(sends.data_ptr()), n_sends,
+            C.c_void_p(keys.data_ptr()), n_keys, max_fragment, C.c_void_p(records.data_ptr()),
+            max_records, C.c_void_p(results.data_ptr()), C.c_void_p(summary.data_ptr()),
+            C.c_void_p(out.data_ptr()), out.numel(), self._stream(stream)), "seal_frames")
+        return records, results, summary
 
 
 class Batcher:

@@ -7,7 +7,9 @@
 //
 // One call = key schedules -> record walk (count, scan, write) -> record crypto -> finalize
 // (stop rules, final content offsets) -> left-shift fix-up for connections whose TLS 1.3
-// records carried padding.  All on one stream, no host synchronisation.
+// records carried padding.  All on one stream, no host synchronisation.  The send side
+// (uvhttp_tls_gpu_seal_frames) = key schedules -> frame scan -> send scan -> record table ->
+// the seal kernels, which read the record count from the device.
 //
 // Record crypto (k_tls_crypt): AES-GCM is integer/bitwise work with no matrix shape — no MFMA.
 // One wavefront per record (<= 1028 GHASH blocks):
@@ -803,7 +805,15 @@ struct SealArgs {
     const KeySched* sched;
     uint32_t n_keys;
     const uint32_t* te0;
+    const uint32_t* n_dev;  // not NULL: the record count is n_dev[0] (at most n), known only on
+                            // the device (uvhttp_tls_gpu_seal_frames); the grid is sized from n
 };
+
+__device__ inline uint32_t seal_count(const SealArgs& a) {
+    if (!a.n_dev) return a.n;
+    const uint32_t n = a.n_dev[0];
+    return n < a.n ? n : a.n;
+}
 
 // One record's GCM on one wave, in two parts around the lane combine.  OPEN: ciphertext at
 // ct[0, clen) -> plaintext content to dst[0, wlen) (wlen = bytes to keep), then tag match +
@@ -1978,13 +1988,14 @@ __global__ OPEN_ATTR void k_tls_seal(SealArgs a) {
     fill_te<TLS_TE_COPIES_REC>(a.te0, te);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t cur = 0xFFFFFFFFu, cur8 = 0xFFFFFFFFu;  // key slots of the wave's 4-bit / 8-bit tables
-    for (uint32_t rb = blockIdx.x * kOpenWaves; rb < a.n; rb += gridDim.x * kOpenWaves) {
+    const uint32_t n = seal_count(a);
+    for (uint32_t rb = blockIdx.x * kOpenWaves; rb < n; rb += gridDim.x * kOpenWaves) {
         const uint32_t r = __builtin_amdgcn_readfirstlane(rb + wave);
         uvhttp_tls_seal_t sr;
         const KeySched* ks = a.sched;
         bool is13 = false;
         uint32_t clen = 0, rlen = 0;
-        bool active = r < a.n && seal_prep(a, r, UVHTTP_TLS_CIPHER_AES_GCM, &sr, &ks, &is13, &clen, &rlen);
+        bool active = r < n && seal_prep(a, r, UVHTTP_TLS_CIPHER_AES_GCM, &sr, &ks, &is13, &clen, &rlen);
         Lanes L{U128{0, 0}, {0, 0, 0, 0}, 0, 0};
         uint8_t* ct = a.out;
         if (active) {
@@ -2049,7 +2060,8 @@ __global__ CHACHA_ATTR void k_tls_seal_chacha(SealArgs a) {
     uint8_t* win = reinterpret_cast<uint8_t*>(wins[threadIdx.x >> 6]);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (uint32_t r = blockIdx.x * kCryptWaves + wave; r < a.n; r += gridDim.x * kCryptWaves) {
+    const uint32_t n = seal_count(a);
+    for (uint32_t r = blockIdx.x * kCryptWaves + wave; r < n; r += gridDim.x * kCryptWaves) {
         uvhttp_tls_seal_t sr;
         const KeySched* ks;
         bool is13;
@@ -2216,6 +2228,228 @@ __global__ __launch_bounds__(kBlock) void k_tls_ws_prefix(const uvhttp_tls_resul
     for (uint64_t o = threadIdx.x; o < n; o += kBlock) q[o] = p[o];
 }
 
+// ---- send side: built frames -> record table (uvhttp_tls_gpu_seal_frames) ---------------------
+//
+// The plan is scans, no lane walks a send's frames: (1) an exclusive scan over the frames of
+// (records at max_fragment, bad frames), shared by every send that names a frame (a broadcast
+// scans once); (2) per send, records / bytes / status from differences of that scan; (3) an
+// exclusive scan over the sends: first_record, out_off, the capacity decision, the totals; (4)
+// one lane per record: binary search of the send by first_record, of the frame by the frame
+// scan, then the chunk.  Then k_tls_seal / k_tls_seal_chacha over the table, their count read
+// from n_total[0].
+
+struct SendWork {         // send pass 1 -> pass 2 / fill
+    uint64_t n_rec;
+    uint64_t bytes;       // record bytes in out
+    int32_t status;
+    uint32_t over;        // bytes a record adds to its content: header, nonce, type byte, tag
+};
+
+struct SendArgs {
+    const uint64_t* frame_off;
+    uint64_t frames_len;
+    uint32_t n_frames;
+    uint32_t max_fragment;
+    const uvhttp_tls_send_t* sends;
+    uint32_t n_sends;
+    uint32_t n_keys;
+    const KeySched* sched;
+    uvhttp_tls_seal_t* records;
+    uint32_t max_records;
+    uvhttp_tls_send_result_t* results;
+    uvhttp_tls_send_summary_t* summary;
+    uint64_t out_cap;
+    uint64_t* fr_rec;     // [n_frames + 1] records of the frames before f
+    uint32_t* fr_bad;     // [n_frames + 1] bad frames before f
+    uint64_t* fblk;       // per 256 frames: [2b] records, [2b+1] bad frames
+    SendWork* sw;
+    uint64_t* sblk;       // per 256 sends: [3b] records, [3b+1] bytes, [3b+2] failed sends
+    uint32_t* s_first;    // [n_sends] first_record
+    uint64_t* s_out;      // [n_sends] out_off
+    uint32_t* n_total;    // [0] records to seal (0 on capacity failure), [1] capacity failed
+};
+
+// frame i's records and whether it is bad (offsets decrease, or reach past frames)
+__device__ inline void send_frame(const SendArgs& a, uint32_t i, uint64_t* rec, uint64_t* bad) {
+    *rec = 0;
+    *bad = 0;
+    if (i >= a.n_frames) return;
+    const uint64_t b = a.frame_off[i], e = a.frame_off[i + 1];
+    if (b > e || e > a.frames_len) {
+        *bad = 1;
+        return;
+    }
+    *rec = (e - b + a.max_fragment - 1) / a.max_fragment;
+}
+
+// exclusive prefix, in place, of n_blocks rows of W block sums; one workgroup
+template <int W>
+__device__ inline void scan_block_sums(uint64_t* blk, uint32_t n_blocks, uint64_t* totals) {
+    const uint32_t per = (n_blocks + kBlock - 1) / kBlock;
+    const uint32_t beg = threadIdx.x * per;
+    const uint32_t fin = beg + per < n_blocks ? beg + per : n_blocks;
+    uint64_t r[W], p[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) r[w] = 0;
+    for (uint32_t b = beg; b < fin; ++b)
+#pragma unroll
+        for (int w = 0; w < W; ++w) r[w] += blk[W * b + w];
+#pragma unroll
+    for (int w = 0; w < W; ++w) p[w] = block_exclusive_sum<uint64_t>(r[w], &totals[w]);
+    for (uint32_t b = beg; b < fin; ++b)
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint64_t v = blk[W * b + w];
+            blk[W * b + w] = p[w];
+            p[w] += v;
+        }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_frame_count(SendArgs a) {
+    uint64_t rec, bad, tr, tb;
+    send_frame(a, blockIdx.x * kBlock + threadIdx.x, &rec, &bad);
+    (void)block_exclusive_sum<uint64_t>(rec, &tr);
+    (void)block_exclusive_sum<uint64_t>(bad, &tb);
+    if (threadIdx.x == 0) {
+        a.fblk[2 * blockIdx.x] = tr;
+        a.fblk[2 * blockIdx.x + 1] = tb;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_frame_scan(SendArgs a, uint32_t n_blocks) {
+    uint64_t t[2];
+    scan_block_sums<2>(a.fblk, n_blocks, t);
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_frame_write(SendArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    uint64_t rec, bad, tr, tb;
+    send_frame(a, i, &rec, &bad);
+    const uint64_t pr = a.fblk[2 * blockIdx.x] + block_exclusive_sum<uint64_t>(rec, &tr);
+    const uint64_t pb = a.fblk[2 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(bad, &tb);
+    if (i <= a.n_frames) {
+        a.fr_rec[i] = pr;
+        a.fr_bad[i] = (uint32_t)pb;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_count(SendArgs a) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    uint64_t n_rec = 0, bytes = 0, failed = 0;
+    if (s < a.n_sends) {
+        const uvhttp_tls_send_t sd = a.sends[s];
+        const uint64_t last = (uint64_t)sd.first_frame + sd.n_frames;
+        int32_t st = 0;
+        uint32_t over = 0;
+        if (sd.key >= a.n_keys || sd.key > 0xFFFFu || a.sched[sd.key].nr == 0) {
+            st = UVHTTP_TLS_REC_ERR_KEY;
+        } else if (last > a.n_frames || a.fr_bad[last] != a.fr_bad[sd.first_frame]) {
+            st = UVHTTP_TLS_REC_ERR_RANGE;
+        } else {
+            const KeySched* k = a.sched + sd.key;
+            over = 5 + 16 + explicit_len(k->version, k->cipher) +
+                   (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
+            n_rec = a.fr_rec[last] - a.fr_rec[sd.first_frame];
+            // (no bad frame in the range: its offsets do not decrease)
+            const uint64_t plain = sd.n_frames ? a.frame_off[last] - a.frame_off[sd.first_frame] : 0;
+            bytes = plain + n_rec * over;
+        }
+        failed = st ? 1 : 0;
+        a.sw[s] = SendWork{n_rec, bytes, st, over};
+    }
+    uint64_t tn, tb, tf;
+    (void)block_exclusive_sum<uint64_t>(n_rec, &tn);
+    (void)block_exclusive_sum<uint64_t>(bytes, &tb);
+    (void)block_exclusive_sum<uint64_t>(failed, &tf);
+    if (threadIdx.x == 0) {
+        a.sblk[3 * blockIdx.x] = tn;
+        a.sblk[3 * blockIdx.x + 1] = tb;
+        a.sblk[3 * blockIdx.x + 2] = tf;
+    }
+}
+
+// exclusive prefix of the per-block sums; capacity decision; totals
+__global__ __launch_bounds__(kBlock) void k_tls_send_scan(SendArgs a, uint32_t n_blocks) {
+    uint64_t t[3];
+    scan_block_sums<3>(a.sblk, n_blocks, t);
+    if (threadIdx.x == 0) {
+        const bool fail = t[0] > a.max_records || t[1] > a.out_cap;
+        a.n_total[0] = fail ? 0u : (uint32_t)t[0];
+        a.n_total[1] = fail ? 1u : 0u;
+        uvhttp_tls_send_summary_t sm;
+        memset(&sm, 0, sizeof(sm));
+        sm.out_bytes = t[1];
+        sm.n_records = t[0] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t[0];
+        sm.n_failed = fail ? a.n_sends : (uint32_t)t[2];
+        *a.summary = sm;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_write(SendArgs a) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    const SendWork sw = s < a.n_sends ? a.sw[s] : SendWork{0, 0, 0, 0};
+    uint64_t tn, tb;
+    const uint64_t first = a.sblk[3 * blockIdx.x] + block_exclusive_sum<uint64_t>(sw.n_rec, &tn);
+    const uint64_t off = a.sblk[3 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(sw.bytes, &tb);
+    if (s >= a.n_sends) return;
+    const uvhttp_tls_send_t sd = a.sends[s];
+    uvhttp_tls_send_result_t r;
+    memset(&r, 0, sizeof(r));
+    r.next_seq = sd.seq;
+    r.status = sw.status;
+    if (a.n_total[1]) {  // capacity: no layout, nothing sealed
+        if (!sw.status) r.status = UVHTTP_TLS_REC_ERR_CAPACITY;
+        a.s_first[s] = 0;
+        a.s_out[s] = 0;
+    } else {
+        r.out_off = off;
+        r.out_len = sw.bytes;
+        r.next_seq = sd.seq + sw.n_rec;
+        r.first_record = (uint32_t)first;
+        r.n_records = (uint32_t)sw.n_rec;
+        r.plain_len = sw.bytes - sw.n_rec * sw.over;
+        a.s_first[s] = (uint32_t)first;
+        a.s_out[s] = off;
+    }
+    a.results[s] = r;
+}
+
+// one lane per record: its send (the last one whose first_record <= r), its frame (the last one
+// of the send whose record prefix <= the record's position in the frame scan), its chunk
+__global__ __launch_bounds__(kBlock) void k_tls_send_fill(SendArgs a) {
+    const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
+    for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
+        uint32_t lo = 0, hi = a.n_sends;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.s_first[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t s = lo;
+        const uvhttp_tls_send_t sd = a.sends[s];
+        const uint64_t k = r - a.s_first[s];
+        const uint64_t pos = a.fr_rec[sd.first_frame] + k;
+        lo = sd.first_frame, hi = sd.first_frame + sd.n_frames;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.fr_rec[mid] <= pos) lo = mid;
+            else hi = mid;
+        }
+        const uint64_t fb = a.frame_off[lo], fe = a.frame_off[lo + 1];
+        const uint64_t cut = (pos - a.fr_rec[lo]) * a.max_fragment;  // content bytes before, in the frame
+        const uint64_t left = fe - fb - cut;
+        uvhttp_tls_seal_t o;
+        o.src_off = fb + cut;
+        o.out_off = a.s_out[s] + (fb - a.frame_off[sd.first_frame]) + cut + k * a.sw[s].over;
+        o.seq = sd.seq + k;
+        o.plain_len = left < a.max_fragment ? (uint32_t)left : a.max_fragment;
+        o.key = (uint16_t)sd.key;
+        o.type = sd.type;
+        o.reserved = 0;
+        a.records[r] = o;
+    }
+}
+
 }  // namespace
 
 // ---- engine ---------------------------------------------------------------------------------
@@ -2226,12 +2460,20 @@ struct uvhttp_tls_gpu_engine {
     void* ws;
     size_t ws_bytes;
     uint32_t cap_keys, cap_streams, cap_records;
+    uint32_t cap_frames, cap_sends;  // seal_frames: frame scan entries, sends
     KeySched* sched;
     RecWork* work;
     StreamWork* sw;
     uint64_t* blk;
     uint32_t* n_total;
     uint32_t* fix;
+    uint64_t* fr_rec;   // seal_frames scratch (SendArgs)
+    uint32_t* fr_bad;
+    uint64_t* fblk;
+    SendWork* send_work;
+    uint64_t* sblk;
+    uint32_t* s_first;
+    uint64_t* s_out;
     int timing;
     hipEvent_t ev[2 * 256];
     int ev_created, ev_used;
@@ -2261,12 +2503,16 @@ static int tls_err(uvhttp_tls_gpu_engine_t* e, int code, const char* what, hipEr
 
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
-static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t streams, uint32_t records) {
-    if (e->ws && keys <= e->cap_keys && streams <= e->cap_streams && records <= e->cap_records)
+static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t streams, uint32_t records,
+                       uint32_t frames = 0, uint32_t sends = 0) {
+    if (e->ws && keys <= e->cap_keys && streams <= e->cap_streams && records <= e->cap_records &&
+        frames <= e->cap_frames && sends <= e->cap_sends)
         return UVHTTP_TLS_GPU_OK;
     keys = keys > e->cap_keys ? keys : e->cap_keys;
     streams = streams > e->cap_streams ? streams : e->cap_streams;
     records = records > e->cap_records ? records : e->cap_records;
+    frames = frames > e->cap_frames ? frames : e->cap_frames;
+    sends = sends > e->cap_sends ? sends : e->cap_sends;
     const size_t nblk = (streams + kBlock - 1) / kBlock + 1;
     const size_t o_sched = 0;
     const size_t o_work = al(o_sched + (size_t)(keys ? keys : 1) * sizeof(KeySched));
@@ -2274,12 +2520,20 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
     const size_t o_blk = al(o_sw + (size_t)(streams ? streams : 1) * sizeof(StreamWork));
     const size_t o_tot = al(o_blk + 2 * nblk * sizeof(uint64_t));
     const size_t o_fix = al(o_tot + 16);
-    const size_t bytes = al(o_fix + (size_t)(streams ? streams : 1) * sizeof(uint32_t));
+    const size_t nfblk = (frames + kBlock - 1) / kBlock + 1, nsblk = (sends + kBlock - 1) / kBlock + 1;
+    const size_t o_frr = al(o_fix + (size_t)(streams ? streams : 1) * sizeof(uint32_t));
+    const size_t o_frb = al(o_frr + (size_t)(frames ? frames : 1) * sizeof(uint64_t));
+    const size_t o_fblk = al(o_frb + (size_t)(frames ? frames : 1) * sizeof(uint32_t));
+    const size_t o_sw2 = al(o_fblk + 2 * nfblk * sizeof(uint64_t));
+    const size_t o_sblk = al(o_sw2 + (size_t)(sends ? sends : 1) * sizeof(SendWork));
+    const size_t o_sfirst = al(o_sblk + 3 * nsblk * sizeof(uint64_t));
+    const size_t o_sout = al(o_sfirst + (size_t)(sends ? sends : 1) * sizeof(uint32_t));
+    const size_t bytes = al(o_sout + (size_t)(sends ? sends : 1) * sizeof(uint64_t));
     if (e->ws) (void)hipFree(e->ws);
     e->ws = nullptr;
     const hipError_t h = hipMalloc(&e->ws, bytes);
     if (h != hipSuccess) {
-        e->cap_keys = e->cap_streams = e->cap_records = 0;
+        e->cap_keys = e->cap_streams = e->cap_records = e->cap_frames = e->cap_sends = 0;
         return tls_err(e, UVHTTP_TLS_GPU_ENOMEM, "hipMalloc tls workspace", h);
     }
     char* b = (char*)e->ws;
@@ -2289,7 +2543,7 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
     if (hz != hipSuccess) {
         (void)hipFree(e->ws);
         e->ws = nullptr;
-        e->cap_keys = e->cap_streams = e->cap_records = 0;
+        e->cap_keys = e->cap_streams = e->cap_records = e->cap_frames = e->cap_sends = 0;
         return tls_err(e, UVHTTP_TLS_GPU_ENOMEM, "hipMemset tls key slots", hz);
     }
     e->work = (RecWork*)(b + o_work);
@@ -2297,10 +2551,19 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
     e->blk = (uint64_t*)(b + o_blk);
     e->n_total = (uint32_t*)(b + o_tot);
     e->fix = (uint32_t*)(b + o_fix);
+    e->fr_rec = (uint64_t*)(b + o_frr);
+    e->fr_bad = (uint32_t*)(b + o_frb);
+    e->fblk = (uint64_t*)(b + o_fblk);
+    e->send_work = (SendWork*)(b + o_sw2);
+    e->sblk = (uint64_t*)(b + o_sblk);
+    e->s_first = (uint32_t*)(b + o_sfirst);
+    e->s_out = (uint64_t*)(b + o_sout);
     e->ws_bytes = bytes;
     e->cap_keys = keys;
     e->cap_streams = streams;
     e->cap_records = records;
+    e->cap_frames = frames;
+    e->cap_sends = sends;
     return UVHTTP_TLS_GPU_OK;
 }
 
@@ -2505,7 +2768,7 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* src, 
     if (n_keys)
         hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
                            keys, n_keys, (const uint32_t*)e->te0, e->sched);
-    SealArgs a{src, src_len, recs, n_records, out, out_cap, e->sched, n_keys, e->te0};
+    SealArgs a{src, src_len, recs, n_records, out, out_cap, e->sched, n_keys, e->te0, nullptr};
     const uint32_t need = (n_records + kCryptWaves - 1) / kCryptWaves;
     const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
     const int tk = tls_timing_begin(e, s);
@@ -2514,6 +2777,95 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* src, 
     hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
     hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
     tls_timing_end(e, tk, s);
+    const hipError_t h = hipGetLastError();
+    if (prev != e->device) (void)hipSetDevice(prev);
+    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
+    return UVHTTP_TLS_GPU_OK;
+}
+
+int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames, uint64_t frames_len,
+                               const uint64_t* frame_off, uint32_t n_frames_total,
+                               const uvhttp_tls_send_t* sends, uint32_t n_sends,
+                               const uvhttp_tls_key_t* keys, uint32_t n_keys, uint32_t max_fragment,
+                               uvhttp_tls_seal_t* records, uint32_t max_records,
+                               uvhttp_tls_send_result_t* results, uvhttp_tls_send_summary_t* summary,
+                               uint8_t* out, uint64_t out_cap, void* stream) {
+    if (!e) {  // no engine: there is none without a device
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
+        return UVHTTP_TLS_GPU_EINVAL;
+    }
+    if ((!frames && frames_len) || (!frame_off && n_frames_total) || (!sends && n_sends) ||
+        (!keys && n_keys) || (!records && max_records) || (!results && n_sends) || !summary ||
+        (!out && out_cap) || max_fragment > 16384)
+        return UVHTTP_TLS_GPU_EINVAL;
+    if (n_sends > (1u << 26) || n_frames_total > (1u << 28) || max_records > (1u << 28))
+        return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / frames / records", hipSuccess);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (prev != e->device) (void)hipSetDevice(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!n_sends) {
+        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
+        if (prev != e->device) (void)hipSetDevice(prev);
+        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
+        return UVHTTP_TLS_GPU_OK;
+    }
+    int rc = tls_reserve(e, n_keys, 1, 1, n_frames_total + 1, n_sends);
+    if (rc) {
+        if (prev != e->device) (void)hipSetDevice(prev);
+        return rc;
+    }
+    tls_call_begin(e, s);
+    if (n_keys)
+        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
+    SendArgs p;
+    p.frame_off = frame_off;
+    p.frames_len = frames_len;
+    p.n_frames = n_frames_total;
+    p.max_fragment = max_fragment ? max_fragment : 16384u;
+    p.sends = sends;
+    p.n_sends = n_sends;
+    p.n_keys = n_keys;
+    p.sched = e->sched;
+    p.records = records;
+    p.max_records = max_records;
+    p.results = results;
+    p.summary = summary;
+    p.out_cap = out_cap;
+    p.fr_rec = e->fr_rec;
+    p.fr_bad = e->fr_bad;
+    p.fblk = e->fblk;
+    p.sw = e->send_work;
+    p.sblk = e->sblk;
+    p.s_first = e->s_first;
+    p.s_out = e->s_out;
+    p.n_total = e->n_total;
+    const uint32_t nfb = (n_frames_total + 1 + kBlock - 1) / kBlock;
+    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_tls_send_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_send_frame_scan, dim3(1), dim3(kBlock), 0, s, p, nfb);
+    hipLaunchKernelGGL(k_tls_send_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_send_count, dim3(nsb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, p, nsb);
+    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, p);
+    if (max_records) {
+        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
+        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
+        hipLaunchKernelGGL(k_tls_send_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, p);
+        // the seal kernels read their count from n_total[0]; grids from max_records, capped
+        SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
+                   e->n_total};
+        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
+        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
+        const int tk = tls_timing_begin(e, s);
+        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
+        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
+        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
+        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
+        tls_timing_end(e, tk, s);
+    }
     const hipError_t h = hipGetLastError();
     if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
