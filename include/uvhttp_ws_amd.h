@@ -725,6 +725,128 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_src
                                uint32_t n_frames, uint8_t* d_out, uint64_t out_cap,
                                uint64_t* d_out_off, void* stream);
 
+/* ---- control replies: PONG and CLOSE echo built on the device after a decode ------------- */
+/* The reply half of uvhttp_ws_process_data (src/uvhttp_websocket.c:1016-1084): every delivered
+ * PING is answered with a PONG carrying the same payload, every delivered CLOSE is echoed.  The
+ * host path does it one frame at a time through the control sink (uvhttp_ws_deliver_stream /
+ * _deliver_batch); these calls build the same frames for a whole decoded batch where it lies in
+ * device memory, in a layout uvhttp_tls_gpu_seal_frames takes as it is, so records in ->
+ * decoded frames -> sealed replies out needs no host step.  build_frames cannot do it: it takes
+ * a host-side frame count, and the number of replies is known only on the device.
+ *
+ * Which frames get a reply.  Connection s considers desc[first_frame, first_frame +
+ * n_delivered), in descriptor order, when d_enable is NULL or d_enable[s] != 0 (d_enable stands
+ * for conn->user_data != NULL with a server context behind it).  The streams form reads
+ * first_frame and n_delivered from d_results[s] on the device, the in-place form n_delivered
+ * from d_batch_summary (one connection, first_frame 0; after decode_inplace or decode_compact,
+ * which both leave control payloads unmasked in the wire), so no host sync sits between decode
+ * and replies.
+ *   PING   a PONG with the ping's unmasked payload (0..125 bytes).
+ *   CLOSE  a CLOSE with an empty payload when payload_len < 2, else payload[0, min(payload_len,
+ *          127)): the code and the reason, as :1048-1066 copies them.
+ *   Everything else gets nothing: data frames, PONG, failing / SKIPPED / INCOMPLETE frames,
+ *   frames past a connection's first failure, descriptors at or past max_frames, and every
+ *   frame of a connection whose result is ERR_CAPACITY, ERR_LAYOUT or ERR_DEVICE.
+ * After a CLOSE.  The reference server's on_close frees the wrapper, so nothing after a
+ * connection's first delivered CLOSE is answered: the default.  UVHTTP_WS_REPLY_AFTER_CLOSE
+ * answers later PINGs and CLOSEs too (the bare library when on_close leaves user_data alone).
+ *
+ * Frame bytes.  Each reply is byte for byte what uvhttp_ws_build_frame(..., opcode, mask =
+ * !is_server, fin = 1) writes (:204-285): a 2-byte header, and for a stream with is_server == 0
+ * four key bytes and a masked payload.  Reply slot j (its index in this call's output) takes
+ * its key from d_mask_keys[j] (k0 = low byte, as uvhttp_ws_build_desc_t.masking_key).
+ * d_mask_keys (max_replies entries) may be NULL only when every stream is a server: a client
+ * stream then gets no replies and status UVHTTP_WS_REPLY_NO_KEYS.
+ *
+ * Layout.  Replies lie back to back in d_out, connections in index order (as their descriptors
+ * lie) and a connection's replies in frame order.  d_out_off[j] is the start of reply j, and
+ * every entry from d_out_off[n_replies] to d_out_off[max_replies] equals the total: d_out /
+ * d_out_off with n_frames_total = max_replies is a valid uvhttp_tls_gpu_seal_frames input as it
+ * lies (frames past the real count have length 0 and give no record).  For connection s the
+ * call writes two uint32_t, first_reply and n_replies, at (char*)d_runs + s * run_stride
+ * (d_runs may be NULL): with a uvhttp_tls_send_t table whose seq, key and type are pre-filled,
+ * pass &sends[0].first_frame and stride 32, then seal_frames with n_sends = n_streams; nothing
+ * is read back (a send with n_frames = 0 succeeds with no record).  first_reply is the number of
+ * replies of the connections before s, also when s has none.
+ *
+ * BAD_RANGE.  When a delivered PING or CLOSE of an enabled connection (answered or not) has a
+ * reply payload that is not inside [0, wire_len), the connection gets status BAD_RANGE and no
+ * replies.  Nothing outside the wire is read.
+ *
+ * Capacity.  If the replies exceed max_replies or their bytes exceed out_cap, nothing is written
+ * to d_out, every d_out_off entry and every run is 0, every per-connection result has
+ * first_reply, n_replies and out_len 0 and status ERR_CAPACITY, and the summary holds the totals
+ * needed with status ERR_CAPACITY, so the caller can size and call again: the rule of
+ * build_frames and seal_frames.
+ *
+ * All pointers are device pointers: d_wire 16-byte aligned, d_desc, d_streams, d_results,
+ * d_batch_summary, d_out_off and d_summary 8, the rest 4 (d_out and d_enable 1).  EINVAL for NULL (d_enable,
+ * d_mask_keys and d_runs excepted) or misaligned arguments, run_stride < 8 or not a multiple of 4
+ * (with d_runs), max_frames or max_replies > 2^28, n_streams > 2^31 (without a device there is
+ * no engine: uvhttp_ws_gpu_engine_create returns ENODEV and nothing is computed on the CPU).
+ * Asynchronous on `stream` under the engine's stream rule.  The call keeps scratch in the engine
+ * (12 bytes per descriptor, 32 per connection, no epoch tags), grown on demand:
+ * graph-capturable once one uncaptured call of the same or a larger shape (max_frames,
+ * n_streams) has been made; a captured call that would allocate fails with ENOMEM. */
+#define UVHTTP_WS_REPLY_AFTER_CLOSE 0x1u  /* flags: keep answering after a connection's first CLOSE */
+
+#define UVHTTP_WS_REPLY_OK 0
+#define UVHTTP_WS_REPLY_ERR_CAPACITY 1  /* the whole call: max_replies or out_cap too small */
+#define UVHTTP_WS_REPLY_BAD_RANGE 2     /* a PING / CLOSE payload range outside the wire */
+#define UVHTTP_WS_REPLY_NO_KEYS 3       /* a client connection and d_mask_keys == NULL */
+
+typedef struct {            /* 16 B, one per connection, device-written */
+    uint32_t first_reply;   /* index of the connection's first reply in d_out_off */
+    uint32_t n_replies;
+    uint32_t out_len;       /* bytes of its replies (saturates at 2^32 - 1) */
+    uint8_t status;         /* UVHTTP_WS_REPLY_* */
+    uint8_t closed;         /* a CLOSE was delivered, whether answered or not */
+    uint8_t reserved[2];
+} uvhttp_ws_reply_conn_t;
+
+typedef struct {            /* 32 B */
+    uint64_t out_bytes;     /* bytes of d_out the call needs */
+    uint32_t n_replies;     /* replies the call needs */
+    uint32_t n_closed_conns;
+    int32_t status;         /* UVHTTP_WS_REPLY_OK or UVHTTP_WS_REPLY_ERR_CAPACITY */
+    uint32_t reserved[3];
+} uvhttp_ws_reply_summary_t;
+
+int uvhttp_ws_gpu_control_replies_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                          uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                          uint32_t max_frames, const uvhttp_ws_stream_t* d_streams,
+                                          const uvhttp_ws_stream_result_t* d_results,
+                                          uint32_t n_streams, const uint8_t* d_enable,
+                                          const uint32_t* d_mask_keys, uint32_t flags,
+                                          uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                                          uint32_t max_replies, uint32_t* d_runs,
+                                          uint32_t run_stride, uvhttp_ws_reply_conn_t* d_conn,
+                                          uvhttp_ws_reply_summary_t* d_summary, void* stream);
+int uvhttp_ws_gpu_control_replies_inplace(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                          uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                          uint32_t n_frames,
+                                          const uvhttp_ws_batch_summary_t* d_batch_summary,
+                                          int32_t is_server, const uint32_t* d_mask_keys,
+                                          uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                                          uint64_t* d_out_off, uint32_t max_replies,
+                                          uint32_t* d_runs, uint32_t run_stride,
+                                          uvhttp_ws_reply_conn_t* d_conn,
+                                          uvhttp_ws_reply_summary_t* d_summary, void* stream);
+/* Host twin (plain C, host copies of the wire and descriptors): the same bytes and result for
+ * one connection, desc[first_frame, first_frame + n_delivered); reply j of the connection
+ * takes mask_keys[j] and starts at out_off[j] (out_off[0] = 0, max_replies + 1 entries, the
+ * tail filled as above), first_reply is 0.  What a pipeline user calls on wait()'s host copies,
+ * and the statement of "device == host".  On capacity nothing is written to out, out_off is
+ * all 0 and the result holds the needed n_replies and out_len with status ERR_CAPACITY.
+ * Returns 0, or -1 for NULL arguments (desc may be NULL when n_delivered is 0, mask_keys when
+ * is_server, out when out_cap is 0). */
+int uvhttp_ws_control_replies(const uint8_t* wire, uint64_t wire_len,
+                              const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                              uint32_t n_delivered, int is_server, int enable,
+                              const uint32_t* mask_keys, uint32_t flags, uint8_t* out,
+                              uint64_t out_cap, uint64_t* out_off, uint32_t max_replies,
+                              uvhttp_ws_reply_conn_t* conn_result);
+
 /* ---- host-memory pipeline (libuv read buffers in, decoded payloads out) ---------------- */
 /* A pipeline owns `depth` slots.  Each slot = a pinned host staging buffer (the caller
  * writes masked frames there, e.g. hands it out from the libuv alloc callback) and a device

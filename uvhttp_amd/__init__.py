@@ -116,6 +116,28 @@ class Utf8FramesSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+REPLY_AFTER_CLOSE = 0x1  # UVHTTP_WS_REPLY_AFTER_CLOSE
+REPLY_OK, REPLY_ERR_CAPACITY, REPLY_BAD_RANGE, REPLY_NO_KEYS = range(4)
+
+
+class ReplyConn(C.Structure):
+    """uvhttp_ws_reply_conn_t (16 B)."""
+    _fields_ = [("first_reply", C.c_uint32), ("n_replies", C.c_uint32), ("out_len", C.c_uint32),
+                ("status", C.c_uint8), ("closed", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("first_reply", "n_replies", "out_len", "status", "closed")}
+
+
+class ReplySummary(C.Structure):
+    """uvhttp_ws_reply_summary_t (32 B)."""
+    _fields_ = [("out_bytes", C.c_uint64), ("n_replies", C.c_uint32), ("n_closed_conns", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("out_bytes", "n_replies", "n_closed_conns", "status")}
+
+
 class Stream(C.Structure):
     """uvhttp_ws_stream_t (64 B)."""
     _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("recv_buffer_size", C.c_uint64),
@@ -346,6 +368,12 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_ws_utf8_judge_frames": (C.c_int, [vp, u64, vp, u32, u32, C.c_int,
                                                   C.POINTER(Utf8State), u32,
                                                   C.POINTER(Utf8ConnVerdict)]),
+        "uvhttp_ws_gpu_control_replies_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp,
+                                                            u32, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
+        "uvhttp_ws_gpu_control_replies_inplace": (C.c_int, [vp, vp, u64, vp, u32, vp, i32, vp, u32, vp,
+                                                            u64, vp, u32, vp, u32, vp, vp, vp]),
+        "uvhttp_ws_control_replies": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, vp,
+                                                u64, vp, u32, C.POINTER(ReplyConn)]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -513,6 +541,30 @@ def utf8_judge_frames(wire, desc, first_frame, n_delivered, open_opcode=0, state
     if rc != 0:
         raise ValueError("uvhttp_ws_utf8_judge_frames: bad argument")
     return out.as_dict()
+
+
+def control_replies(wire, desc, first_frame, n_delivered, is_server=1, enable=1, mask_keys=None,
+                    flags=0, out_cap=None, max_replies=None, wire_len=None):
+    """uvhttp_ws_control_replies: the host twin of GpuEngine.control_replies_streams / _inplace
+    for one connection.  `wire` / `desc` as utf8_judge_frames; mask_keys = a sequence of 32-bit
+    keys, one per reply slot (None: no table).  out_cap / max_replies default to what
+    n_delivered replies can need.  -> (out bytes [out_len], out_off list [max_replies + 1],
+    ReplyConn.as_dict())."""
+    wb = _host_buf(wire)
+    db = _host_buf(desc)
+    max_replies = n_delivered if max_replies is None else max_replies
+    out_cap = 131 * n_delivered if out_cap is None else out_cap
+    out = (C.c_uint8 * max(1, out_cap))()
+    off = (C.c_uint64 * (max_replies + 1))()
+    kb = None if mask_keys is None else (C.c_uint32 * max(1, len(mask_keys)))(*mask_keys)
+    res = ReplyConn()
+    n = len(wire) if wire_len is None else wire_len
+    rc = lib().uvhttp_ws_control_replies(wb, n, db, first_frame, n_delivered, is_server, enable, kb,
+                                         flags, out, out_cap, off, max_replies, C.byref(res))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_control_replies: bad argument")
+    ok = res.status != REPLY_ERR_CAPACITY
+    return bytes(out)[: res.out_len if ok else 0], list(off), res.as_dict()
 
 
 class WsConnection:
@@ -869,6 +921,75 @@ class GpuEngine:
             C.c_void_p(verdict.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
             "validate_utf8_inplace")
         return verdict, summary
+
+    def _replies_out(self, n_streams, max_replies, out_cap, out, out_off, conn, summary):
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = t.zeros(max(16, out_cap), dtype=t.uint8, device=dev)
+        if out_off is None:
+            out_off = t.zeros(max_replies + 1, dtype=t.int64, device=dev)
+        if conn is None:
+            conn = t.zeros(max(1, n_streams) * C.sizeof(ReplyConn), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(ReplySummary), dtype=t.uint8, device=dev)
+        return out, out_off, conn, summary
+
+    @staticmethod
+    def _ptr(x):
+        return C.c_void_p(x.data_ptr() if x is not None else None)
+
+    def control_replies_streams(self, wire, desc, max_frames, streams_dev, results, n_streams,
+                                max_replies, out_cap, enable=None, mask_keys=None, flags=0, out=None,
+                                out_off=None, runs=None, run_stride=8, conn=None, summary=None,
+                                wire_len=None, stream=None):
+        """uvhttp_ws_gpu_control_replies_streams after decode_streams / decode_reads over the same
+        device tensors: the PONG / CLOSE-echo frames of every connection's delivered PINGs and
+        CLOSEs.  enable = device uint8[n_streams] or None, mask_keys = device int32[max_replies] or
+        None, runs = a device tensor (or a view into a uvhttp_tls_send_t table at first_frame) that
+        takes (first_reply, n_replies) every run_stride bytes.  Returns (out, out_off, conn,
+        summary) device tensors: the frames, max_replies + 1 int64 offsets, n_streams 16-byte
+        uvhttp_ws_reply_conn_t and the 32-byte uvhttp_ws_reply_summary_t."""
+        out, out_off, conn, summary = self._replies_out(n_streams, max_replies, out_cap, out, out_off,
+                                                        conn, summary)
+        self._check(self._L.uvhttp_ws_gpu_control_replies_streams(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), max_frames, C.c_void_p(streams_dev.data_ptr()),
+            C.c_void_p(results.data_ptr()), n_streams, self._ptr(enable), self._ptr(mask_keys), flags,
+            C.c_void_p(out.data_ptr()), out_cap, C.c_void_p(out_off.data_ptr()), max_replies,
+            self._ptr(runs), run_stride, C.c_void_p(conn.data_ptr()), C.c_void_p(summary.data_ptr()),
+            self._stream(stream)), "control_replies_streams")
+        return out, out_off, conn, summary
+
+    def control_replies_inplace(self, wire, desc, n_frames, batch_summary, max_replies, out_cap,
+                                is_server=1, mask_keys=None, flags=0, out=None, out_off=None,
+                                runs=None, run_stride=8, conn=None, summary=None, wire_len=None,
+                                stream=None):
+        """uvhttp_ws_gpu_control_replies_inplace after decode_inplace / decode_compact (with
+        descriptors) over the same device tensors: one connection.  Returns as
+        control_replies_streams."""
+        out, out_off, conn, summary = self._replies_out(1, max_replies, out_cap, out, out_off, conn,
+                                                        summary)
+        self._check(self._L.uvhttp_ws_gpu_control_replies_inplace(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), n_frames, C.c_void_p(batch_summary.data_ptr()), is_server,
+            self._ptr(mask_keys), flags, C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_replies, self._ptr(runs), run_stride,
+            C.c_void_p(conn.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
+            "control_replies_inplace")
+        return out, out_off, conn, summary
+
+    @staticmethod
+    def read_reply_conns(conn, n):
+        """host copy of the first n per-connection reply results -> [dict] (ReplyConn.as_dict)"""
+        sz = C.sizeof(ReplyConn)
+        raw = bytes(conn[: n * sz].cpu().numpy().tobytes())
+        return [ReplyConn.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_reply_summary(summary) -> dict:
+        raw = bytes(summary.cpu().numpy().tobytes())
+        return ReplySummary.from_buffer_copy(raw).as_dict()
 
     @staticmethod
     def read_utf8_conn_verdicts(verdict, n):

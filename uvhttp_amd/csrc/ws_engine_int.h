@@ -25,6 +25,8 @@ UVWS_INTERNAL int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* 
 // the call's stream like every other scratch block; null when it cannot grow (a captured call
 // that would allocate, or out of memory).  Call between uvws_call_enter and uvws_call_leave.
 UVWS_INTERNAL void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
+// The control replies' scratch (ws_replies_gpu.hip), by the same rule.
+UVWS_INTERNAL void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"
 

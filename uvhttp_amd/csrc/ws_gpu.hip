@@ -5637,6 +5637,8 @@ struct uvhttp_ws_gpu_engine {
     uint64_t dscr_cap;
     void* u8_mem;              // the frame UTF-8 validator's scratch (utf8_gpu.hip; uvws_utf8_scratch)
     uint64_t u8_bytes;
+    void* rp_mem;              // the control replies' scratch (ws_replies_gpu.hip; uvws_replies_scratch)
+    uint64_t rp_bytes;
     uint32_t* ctl;             // device control words (kCtl*), own allocation
     uint32_t faults_seen;      // ctl[kCtlFaults] at the last engine_sync
     uint32_t max_polls;        // look-back wait bound (UVHTTP_WS_MAX_POLLS: tests)
@@ -5842,6 +5844,7 @@ void uvhttp_ws_gpu_engine_free(uvhttp_ws_gpu_engine_t* e) {
     scratch_free(e, e->dscr);
     scratch_free(e, e->sp_mem);
     scratch_free(e, e->u8_mem);
+    scratch_free(e, e->rp_mem);
     if (e->pool_ok) (void)hipStreamSynchronize(nullptr);
     if (e->ctl) (void)hipFree(e->ctl);
     if (e->stamp_mem) (void)hipFree(e->stamp_mem);
@@ -6414,6 +6417,19 @@ void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s
     }
     e->u8_bytes = bytes;
     return e->u8_mem;
+}
+
+// ... and the control replies' (ws_replies_gpu.hip)
+void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
+    if (e->rp_mem && e->rp_bytes >= bytes) return e->rp_mem;
+    if (e->capturing) return nullptr;
+    e->rp_bytes = 0;
+    if (scratch_grow(e, &e->rp_mem, bytes, false, s, true) != hipSuccess) {
+        e->rp_mem = nullptr;
+        return nullptr;
+    }
+    e->rp_bytes = bytes;
+    return e->rp_mem;
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot

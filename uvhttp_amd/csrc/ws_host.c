@@ -739,3 +739,72 @@ int uvhttp_ws_utf8_judge_frames(const uint8_t* wire, uint64_t wire_len,
     out->status = status;
     return 0;
 }
+
+/* ---- control replies: PONG / CLOSE echo frames of one connection's delivered frames -------- */
+/* The host twin of uvhttp_ws_gpu_control_replies_streams / _inplace, and what dispatch_frame
+ * hands the control sink (on_close_frame's echo, the PING branch), written as the frames
+ * uvhttp_ws_build_frame(..., opcode, mask = !is_server, fin = 1) makes of them. */
+int uvhttp_ws_control_replies(const uint8_t* wire, uint64_t wire_len,
+                              const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                              uint32_t n_delivered, int is_server, int enable,
+                              const uint32_t* mask_keys, uint32_t flags, uint8_t* out,
+                              uint64_t out_cap, uint64_t* out_off, uint32_t max_replies,
+                              uvhttp_ws_reply_conn_t* r) {
+    if (r == NULL || out_off == NULL || (desc == NULL && n_delivered != 0) ||
+        (wire == NULL && wire_len != 0) || (out == NULL && out_cap != 0))
+        return -1;
+    memset(r, 0, sizeof(*r));
+    for (uint64_t j = 0; j <= max_replies; ++j) out_off[j] = 0;
+    const int masked = !is_server;
+    const uint64_t hdr = masked ? 6u : 2u;
+    if (enable && masked && mask_keys == NULL) r->status = UVHTTP_WS_REPLY_NO_KEYS;
+    /* two passes over the same walk: size (and the statuses), then emit */
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t n = 0, bytes = 0;
+        int closed = 0;
+        for (uint32_t i = 0; i < n_delivered; ++i) {
+            const uvhttp_ws_frame_desc_t* d = &desc[(uint64_t)first_frame + i];
+            if (d->status != UVHTTP_WS_FRAME_OK) continue; /* not delivered: no reply */
+            const int op = d->opcode;
+            if (op != UVHTTP_WS_OPCODE_PING && op != UVHTTP_WS_OPCODE_CLOSE) continue;
+            const int after = closed;
+            if (op == UVHTTP_WS_OPCODE_CLOSE) closed = 1;
+            if (pass == 0 && op == UVHTTP_WS_OPCODE_CLOSE) r->closed = 1;
+            if (!enable) continue;
+            uint64_t len = d->payload_len;
+            if (op == UVHTTP_WS_OPCODE_CLOSE) len = len < 2 ? 0 : len > 127 ? 127 : len;
+            if (len > 125) len = 125; /* a delivered control frame has at most 125 bytes */
+            if (pass == 0 && len != 0 && !utf8_range_ok(wire_len, d->payload_off, len) &&
+                r->status == UVHTTP_WS_REPLY_OK)
+                r->status = UVHTTP_WS_REPLY_BAD_RANGE;
+            if (after && !(flags & UVHTTP_WS_REPLY_AFTER_CLOSE)) continue;
+            if (pass == 1) {
+                uint8_t* o = out + bytes;
+                const uint32_t key = masked ? mask_keys[n] : 0u;
+                o[0] = (uint8_t)(0x80u | (op == UVHTTP_WS_OPCODE_PING ? UVHTTP_WS_OPCODE_PONG
+                                                                      : UVHTTP_WS_OPCODE_CLOSE));
+                o[1] = (uint8_t)((masked ? 0x80u : 0u) | len);
+                if (masked)
+                    for (int k = 0; k < 4; ++k) o[2 + k] = (uint8_t)(key >> (8 * k));
+                for (uint64_t b = 0; b < len; ++b)
+                    o[hdr + b] = (uint8_t)(wire[d->payload_off + b] ^ (uint8_t)(key >> (8 * (b & 3))));
+                out_off[n] = bytes;
+            }
+            n++;
+            bytes += hdr + len;
+        }
+        if (pass == 0) {
+            if (r->status != UVHTTP_WS_REPLY_OK) return 0; /* NO_KEYS / BAD_RANGE: no replies */
+            r->n_replies = (uint32_t)n;
+            r->out_len = bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
+            if (n > max_replies || bytes > out_cap) {
+                r->status = UVHTTP_WS_REPLY_ERR_CAPACITY;
+                return 0;
+            }
+            if (n == 0) return 0;
+        } else {
+            for (uint64_t j = n; j <= max_replies; ++j) out_off[j] = bytes;
+        }
+    }
+    return 0;
+}
