@@ -22,7 +22,8 @@ CFLAGS := -O2 -DNDEBUG -fPIC -std=gnu11 -Iinclude -Wall -Wextra -Werror
 
 all: $(LIB) $(TESTLIB) oracle ctests probes
 
-ENGINE_INT := uvhttp_amd/csrc/ws_engine_int.h
+DEVICE_GUARD := uvhttp_amd/csrc/device_guard.h
+ENGINE_INT := uvhttp_amd/csrc/ws_engine_int.h $(DEVICE_GUARD)
 UTF8_RULES := uvhttp_amd/csrc/utf8_rules.h
 
 $(BUILD)/ws_gpu.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
@@ -44,7 +45,7 @@ $(BUILD)/ws_replies_gpu.o: uvhttp_amd/csrc/ws_replies_gpu.hip include/uvhttp_ws_
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(BUILD)/tls_gpu.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h
+$(BUILD)/tls_gpu.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h $(DEVICE_GUARD)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
@@ -60,7 +61,7 @@ $(BUILD)/ws_gpu_exp.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h $(ENGI
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXP) -c -o $@ $<
 
-$(BUILD)/tls_gpu_exp.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h
+$(BUILD)/tls_gpu_exp.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h $(DEVICE_GUARD)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXP) -c -o $@ $<
 

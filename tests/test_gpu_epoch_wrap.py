@@ -131,7 +131,7 @@ def _oracle_delivers_all(shape):
 def test_stream_spec_across_host_wrap(torch, monkeypatch, pair):
     """Six calls alternating two shapes on fresh engines that start three calls before the last
     host epoch and never capture a graph: every call must take the speculative path and equal
-    the walk engine and the oracle.  Left uncleared, the tile claims in sp_mem (conn_tile,
+    the walk engine and the oracle.  Left uncleared, the tile claims in kScrSp (conn_tile,
     claimed with a plain atomicMax of (epoch << 32) | ~connection) of the calls before the wrap
     outrank every claim after it: tag_get finds no connection for the tile, k_sspec_tiles writes no
     SpecTile, k_sspec_pass returns at "no connection's frames touch the tile" without a break, and
@@ -195,7 +195,7 @@ def test_stream_calls_full_cycle(torch, monkeypatch, variant):
 
 def test_fused_walk_full_cycle(torch, monkeypatch):
     """The same cycle through k_swalk_fused (UVHTTP_WS_WALK_FUSE=1, no speculation), whose tags
-    live in ss_mem: the look-back records (srec, (epoch << 2) | kind) and ctr[2], the epoch of the
+    live in kScrSs: the look-back records (srec, (epoch << 2) | kind) and ctr[2], the epoch of the
     latest call over capacity.  Every third call has a frame capacity below its frames
     (ERR_CAPACITY, nothing decoded); left uncleared, ctr[2] makes the good call that takes the
     same epoch a cycle later report ERR_CAPACITY too."""
@@ -233,10 +233,10 @@ def test_stride_and_table_calls_full_cycle(torch, monkeypatch, kind):
       ctl[kCtlGate] = epoch and is decoded again by k_plan + k_spec_fix.  A stale gate sends the
       good call of that epoch a cycle later the same way (read off the stamps);
     desc_emit — in place with descriptors through k_desc_emit (asserted from the stamps), the
-      broken call a reserved bit: first_bad / spec_bad and the scan's records in ws_mem;
+      broken call a reserved bit: first_bad / spec_bad and the scan's records in kScrWs;
     fused_inplace — 600 frames of 60 and of 1000 payload bytes in place, the broken call with one
       frame a byte longer (ERR_LAYOUT): tile_first, first_bad and k_plan's look-back records
-      ((epoch << 2) | kind, accepted by ==) in ws_mem;
+      ((epoch << 2) | kind, accepted by ==) in kScrWs;
     offset_table — 3000 and 40 frames by offset table, in place and compact, the broken call with
       failing frames: tile_first, arena_first, first_bad, the look-back records."""
     e = _engine(monkeypatch, _wrap_env("period"), stamps=True)
@@ -286,7 +286,7 @@ def test_build_frames_across_wrap(torch, monkeypatch, wrap, path):
     """build_frames, server and masked frames mixed, alternating 2000 x 60-byte frames (the small-
     frame emit) and 40 x 20000-byte frames (the >= 4 KiB shape) across the host wrap and through
     full cycles, against the oracle's build_frame.  The output map records (BuildRec.tag, ==) live
-    in bs_mem; "tiles" (UVHTTP_WS_BUILD_FRAMES=0) makes the small frames take map records too, at
+    in kScrBs; "tiles" (UVHTTP_WS_BUILD_FRAMES=0) makes the small frames take map records too, at
     another map granularity than the large ones."""
     import uvhttp_amd as U
     env = _wrap_env(wrap)

@@ -37,6 +37,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "device_guard.h"
 #include "uvhttp_tls_amd.h"
 #include "uvhttp_ws_amd.h"
 
@@ -2620,9 +2621,7 @@ int uvhttp_tls_gpu_engine_create(int device, uvhttp_tls_gpu_engine_t** out) {
     uvhttp_tls_gpu_engine_t* e = (uvhttp_tls_gpu_engine_t*)calloc(1, sizeof(*e));
     if (!e) return UVHTTP_TLS_GPU_ENOMEM;
     e->device = device;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
+    DeviceGuard dev(device);
     hipError_t h = hipMalloc(&e->te0, 256 * sizeof(uint32_t));
     if (h == hipSuccess) {
         hipLaunchKernelGGL(k_tls_te0, dim3(1), dim3(64), 0, 0, e->te0);
@@ -2633,7 +2632,6 @@ int uvhttp_tls_gpu_engine_create(int device, uvhttp_tls_gpu_engine_t** out) {
 #ifdef UVWS_EXPERIMENTS  // (A/B builds only: the product library reads no environment)
     if (const char* g = getenv("UVHTTP_TLS_CRYPT_GRID")) e->crypt_grid = atoi(g) > 0 ? atoi(g) : e->crypt_grid;
 #endif
-    (void)hipSetDevice(prev);
     if (h != hipSuccess) {
         if (e->te0) (void)hipFree(e->te0);
         free(e);
@@ -2645,14 +2643,11 @@ int uvhttp_tls_gpu_engine_create(int device, uvhttp_tls_gpu_engine_t** out) {
 
 void uvhttp_tls_gpu_engine_free(uvhttp_tls_gpu_engine_t* e) {
     if (!e) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     if (e->ws) (void)hipFree(e->ws);
     if (e->te0) (void)hipFree(e->te0);
     if (e->order_ev) (void)hipEventDestroy(e->order_ev);
     for (int k = 0; k < e->ev_created; ++k) (void)hipEventDestroy(e->ev[k]);
-    (void)hipSetDevice(prev);
     free(e);
 }
 
@@ -2688,14 +2683,9 @@ int uvhttp_tls_gpu_open_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* wire,
     if (n_streams > (1u << 26) || max_records > (1u << 28))
         return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many streams / records", hipSuccess);
     if (!n_streams) return UVHTTP_TLS_GPU_OK;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     int rc = tls_reserve(e, n_keys, n_streams, max_records);
-    if (rc) {
-        if (prev != e->device) (void)hipSetDevice(prev);
-        return rc;
-    }
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     tls_call_begin(e, s);
     TlsArgs a;
@@ -2743,7 +2733,6 @@ int uvhttp_tls_gpu_open_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* wire,
     hipLaunchKernelGGL(k_tls_finalize, dim3(nb), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_tls_fixup, dim3(n_streams), dim3(kBlock), 0, s, a);
     const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
     return UVHTTP_TLS_GPU_OK;
 }
@@ -2755,14 +2744,9 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* src, 
     if (!e || (!src && src_len) || (!recs && n_records) || (!keys && n_keys) || (!out && out_cap))
         return UVHTTP_TLS_GPU_EINVAL;
     if (!n_records) return UVHTTP_TLS_GPU_OK;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     int rc = tls_reserve(e, n_keys, 1, 1);
-    if (rc) {
-        if (prev != e->device) (void)hipSetDevice(prev);
-        return rc;
-    }
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     tls_call_begin(e, s);
     if (n_keys)
@@ -2778,7 +2762,6 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* src, 
     hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
     tls_timing_end(e, tk, s);
     const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
     return UVHTTP_TLS_GPU_OK;
 }
@@ -2801,21 +2784,15 @@ int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames
         return UVHTTP_TLS_GPU_EINVAL;
     if (n_sends > (1u << 26) || n_frames_total > (1u << 28) || max_records > (1u << 28))
         return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / frames / records", hipSuccess);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     hipStream_t s = (hipStream_t)stream;
     if (!n_sends) {
         const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
-        if (prev != e->device) (void)hipSetDevice(prev);
         if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
         return UVHTTP_TLS_GPU_OK;
     }
     int rc = tls_reserve(e, n_keys, 1, 1, n_frames_total + 1, n_sends);
-    if (rc) {
-        if (prev != e->device) (void)hipSetDevice(prev);
-        return rc;
-    }
+    if (rc) return rc;
     tls_call_begin(e, s);
     if (n_keys)
         hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
@@ -2867,7 +2844,6 @@ int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames
         tls_timing_end(e, tk, s);
     }
     const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
     return UVHTTP_TLS_GPU_OK;
 }
@@ -2881,9 +2857,7 @@ int uvhttp_tls_gpu_ws_streams(uvhttp_tls_gpu_engine_t* e, const uvhttp_tls_resul
         (prefix_src && !prefix_off))
         return UVHTTP_TLS_GPU_EINVAL;
     if (!n_streams) return UVHTTP_TLS_GPU_OK;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     hipStream_t s = (hipStream_t)stream;
     tls_call_begin(e, s);
     if (prefix_src)
@@ -2893,7 +2867,6 @@ int uvhttp_tls_gpu_ws_streams(uvhttp_tls_gpu_engine_t* e, const uvhttp_tls_resul
                        s, results, records, n_streams, streams, (uvhttp_ws_stream_t*)ws_streams,
                        read_end);
     const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
     return UVHTTP_TLS_GPU_OK;
 }

@@ -651,11 +651,9 @@ int fu_run(uvhttp_ws_gpu_engine_t* e, FuArgs a, void* stream, const char* what) 
         hipLaunchKernelGGL((k_fu_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg2, blocks);
         hipLaunchKernelGGL(k_fu_segs, dim3(blocks), dim3(kBlock), 0, s, a);
         const uint64_t tiles = (a.wire_len + kTileBytes - 1) / kTileBytes;
-        const uint64_t max_tiles = 1ull << 24;
-        for (uint64_t tb = 0; tb < tiles; tb += max_tiles) {
-            const uint32_t grid = (uint32_t)(tiles - tb < max_tiles ? tiles - tb : max_tiles);
+        for_grid_chunks(tiles, [&](uint32_t grid, uint64_t tb) {
             hipLaunchKernelGGL(k_fu_tiles, dim3(grid), dim3(kBlock), 0, s, a, tb, blocks);
-        }
+        });
     }
     if (grid_s) hipLaunchKernelGGL(k_fu_finish, dim3(grid_s), dim3(kBlock), 0, s, a);
     return uvws_call_leave(e, prev, what);

@@ -6,26 +6,38 @@
 
 #include <hip/hip_runtime.h>
 
+#include "device_guard.h"
 #include "uvhttp_ws_amd.h"
 
 #define UVWS_INTERNAL __attribute__((visibility("hidden")))
 
+// The dispatch packet counts work-items in 32 bits, so a pass of `tiles` workgroups goes out in
+// launches of at most 2^24: launch(grid, tile_base) once per piece, none for an empty pass.
+constexpr uint64_t kMaxGrid = 1ull << 24;
+template <class F>
+static inline void for_grid_chunks(uint64_t tiles, F&& launch) {
+    for (uint64_t tb = 0; tb < tiles; tb += kMaxGrid)
+        launch((uint32_t)(tiles - tb < kMaxGrid ? tiles - tb : kMaxGrid), tb);
+}
+
 extern "C" {
 
-// Start of a call: makes the engine's device current (returns the one that was), notes whether
-// `s` is being captured and, when the call names another stream than the previous call, makes
-// `s` wait for the work already queued on that one (call_begin in ws_gpu.hip).
+// Start of a call (EngineCall in ws_gpu.hip, in two halves): makes the engine's device current
+// (returns the one that was), then notes whether `s` is being captured and, when the call names
+// another stream than the previous call, makes `s` wait for the work already queued on that one
+// (call_begin).
 UVWS_INTERNAL int uvws_call_enter(uvhttp_ws_gpu_engine_t* e, hipStream_t s);
-// End of a call: leaves capture mode, restores the device, and turns a pending HIP launch error
-// into UVHTTP_WS_GPU_ELAUNCH with last_error set ("<what>: <hip error>"); else OK.
+// End of a call: turns a pending HIP launch error into UVHTTP_WS_GPU_ELAUNCH with last_error set
+// ("<what>: <hip error>"), else OK; leaves capture mode and restores the device.
 UVWS_INTERNAL int uvws_call_leave(uvhttp_ws_gpu_engine_t* e, int prev_device, const char* what);
 // Sets last_error and returns `code`.
 UVWS_INTERNAL int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what);
 // The frame UTF-8 validator's engine-owned scratch of at least `bytes` (not zeroed), grown on
-// the call's stream like every other scratch block; null when it cannot grow (a captured call
-// that would allocate, or out of memory).  Call between uvws_call_enter and uvws_call_leave.
+// the call's stream by the rule of every scratch block (scratch_fit in ws_gpu.hip); null when
+// it cannot grow (a captured call that would allocate, or out of memory).  Call between
+// uvws_call_enter and uvws_call_leave.
 UVWS_INTERNAL void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
-// The control replies' scratch (ws_replies_gpu.hip), by the same rule.
+// The control replies' scratch (ws_replies_gpu.hip), likewise.
 UVWS_INTERNAL void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"

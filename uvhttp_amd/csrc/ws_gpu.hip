@@ -5553,7 +5553,7 @@ __global__ __launch_bounds__(kBlock) void k_gen_frames(uint8_t* wire, uint32_t f
 // ("Epoch-tagged state").  The blocks are the engine's as of the capture, like
 // every other pointer a captured call holds.
 struct EpochClear {
-    uint64_t* p[4];  // ws_mem, bs_mem, sp_mem, ss_mem (null: not allocated)
+    uint64_t* p[4];  // kScrWs, kScrBs, kScrSp, kScrSs (null: not allocated)
     uint64_t n[4];   // their sizes in 8-byte words
 };
 __global__ __launch_bounds__(kBlock) void k_epoch(uint32_t* ctl, EpochClear c) {
@@ -5587,10 +5587,28 @@ __global__ __launch_bounds__(kBlock) void k_epoch(uint32_t* ctl, EpochClear c) {
 // ======================================================================================
 // engine + C ABI
 // ======================================================================================
+// An engine-owned scratch block: its device memory and the bytes allocated (0 exactly when p is
+// null).  scratch_fit is the one place a block grows; engine_free releases them all.
+struct Scratch {
+    void* p;
+    size_t bytes;
+};
+enum ScratchId {
+    kScrWs,       // the workspace (Workspace; cap_frames / cap_tiles / cap_arena_tiles)
+    kScrSs,       // stream-decode scratch (StreamScratch; ss_frames / ss_reads)
+    kScrBs,       // send-side output-map records (BuildRec per map tile, + 1 spare)
+    kScrWt,       // single-pass walk scratch (frame starts per connection slice, 4 bytes each)
+    kScrWr,       // the wave walk's frame records (parallel to kScrWt, 8 bytes each)
+    kScrDesc,     // descriptor scratch for d_desc == NULL calls
+    kScrSp,       // the speculative stream decode's scratch (spec_layout(sp_streams, sp_tiles))
+    kScrUtf8,     // the frame UTF-8 validator's (utf8_frames_gpu.hip; uvws_utf8_scratch)
+    kScrReplies,  // the control replies' (ws_replies_gpu.hip; uvws_replies_scratch)
+    kScrCount
+};
+
 struct uvhttp_ws_gpu_engine {
     int device;
-    void* ws_mem;
-    size_t ws_bytes;
+    Scratch scr[kScrCount];
     uint32_t cap_frames;
     uint64_t cap_tiles, cap_arena_tiles;
     Workspace ws;
@@ -5605,40 +5623,24 @@ struct uvhttp_ws_gpu_engine {
     int rec_lookback;          // fused path: records scanned by k_plan (1) or reduce-then-scan (0)
     int plan_wide;             // records: k_plan with 1024-thread blocks (UVHTTP_WS_PLAN_WIDE=1; A/B)
     int walk_mode;             // stream frame discovery: 0 automatic, 1 lane, 2 wave
-    void* ss_mem;              // stream-decode scratch
-    uint32_t ss_frames, ss_reads;
-    size_t ss_bytes;
+    uint32_t ss_frames, ss_reads;  // capacities of the stream-decode scratch
     StreamScratch ss;
-    void* wt_mem;              // single-pass walk scratch (frame starts per connection slice)
-    uint64_t wt_cap;
-    void* wr_mem;              // the wave walk's frame records (parallel to wt_mem)
-    uint64_t wr_cap;
     int wr_rec_on;             // UVHTTP_WS_WALK_REC=0: k_stream_desc gathers every header (A/B)
     int walk_single_off;       // UVHTTP_WS_WALK_SINGLE=0: always walk twice (tests, A/B)
     int walk_fuse;             // UVHTTP_WS_WALK_FUSE=1: k_swalk_fused for the single-pass wave walk
     int desc_scan_off;         // UVHTTP_WS_DESC_SCAN=0: k_swalk_scan before k_stream_desc always (A/B)
     int stream_spec;           // stream calls try the speculative decode first (k_sspec_*;
                                // UVHTTP_WS_STREAM_SPEC=0: the walk always)
-    void* sp_mem;              // its scratch: SpecConn per connection, block counts, tile claims
-    uint32_t sp_streams;
+    uint32_t sp_streams;       // its scratch: SpecConn per connection, block counts, tile claims
     uint64_t sp_tiles;
-    size_t sp_bytes;           // spec_layout(sp_streams, sp_tiles).bytes
     int spec_on;               // compact stride batches: the speculative pass (UVHTTP_WS_SPEC=0: off)
     uint64_t spec_max_avg;     // ... up to this many wire bytes per frame (UVHTTP_WS_SPEC_MAX)
     int time_chain;            // UVHTTP_WS_TIME_CHAIN=1: stream decode timing brackets the whole
                                // kernel chain (walk .. payload), not only the payload kernel
-    void* bs_mem;              // send-side output-map records (BuildRec per map tile)
-    uint64_t bs_tiles;
     int build_small;           // emit shape for frames < 4 KiB (UVHTTP_WS_BUILD_SMALL, tuning)
     uint64_t build_frames_max; // frame-grouped LDS emit below this average frame (UVHTTP_WS_BUILD_FRAMES; 0 = off)
     int compact_mode;          // 0 automatic, 1 arena-driven gather, 2 wire-driven scatter
     int sum_fast;              // summary-only stride decode in one payload pass (UVHTTP_WS_SUMMARY_FAST=0: off)
-    uvhttp_ws_frame_desc_t* dscr;  // descriptor scratch for d_desc == NULL calls
-    uint64_t dscr_cap;
-    void* u8_mem;              // the frame UTF-8 validator's scratch (utf8_gpu.hip; uvws_utf8_scratch)
-    uint64_t u8_bytes;
-    void* rp_mem;              // the control replies' scratch (ws_replies_gpu.hip; uvws_replies_scratch)
-    uint64_t rp_bytes;
     uint32_t* ctl;             // device control words (kCtl*), own allocation
     uint32_t faults_seen;      // ctl[kCtlFaults] at the last engine_sync
     uint32_t max_polls;        // look-back wait bound (UVHTTP_WS_MAX_POLLS: tests)
@@ -5661,7 +5663,6 @@ struct uvhttp_ws_gpu_engine {
     char err[256];
 };
 
-static void scratch_free(uvhttp_ws_gpu_engine_t* e, void* p);
 static int set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what, hipError_t h) {
     if (e) snprintf(e->err, sizeof(e->err), "%s: %s", what, h == hipSuccess ? "" : hipGetErrorString(h));
     return code;
@@ -5671,11 +5672,29 @@ template <int BLOCK, int VPT>
 static void launch_emit(const BuildArgs& b, uint32_t n_frames, uint64_t out_cap, hipStream_t s) {
     const uint64_t tile_bytes = (uint64_t)BLOCK * VPT * 16;
     const uint64_t n_ptiles = (out_cap + tile_bytes - 1) / tile_bytes;
-    const uint64_t max_tiles = (1ull << 24);
-    for (uint64_t tb = 0; n_frames && tb < n_ptiles; tb += max_tiles) {
-        const uint32_t grid_p = (uint32_t)((n_ptiles - tb) < max_tiles ? (n_ptiles - tb) : max_tiles);
+    for_grid_chunks(n_frames ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
         hipLaunchKernelGGL((kb_emit<BLOCK, VPT>), dim3(grid_p), dim3(BLOCK), 0, s, b, tb);
-    }
+    });
+}
+
+// The payload tile shapes, listed once: workgroup size and 16-byte vectors per lane.  set_tile
+// accepts these, and the payload kernels are instantiated for exactly these.
+template <int B, int V>
+struct Tile {
+    static constexpr int block = B, vpt = V;
+};
+template <class... T>
+struct TileList {};
+using TileShapes = TileList<Tile<64, 1>, Tile<64, 2>, Tile<64, 4>, Tile<128, 1>, Tile<128, 2>,
+                            Tile<256, 1>, Tile<256, 2>, Tile<256, 4>>;
+// Calls f(Tile<block, vpt>{}) for the listed shape; false (f not called) for any other.
+template <class F, class... T>
+static bool tile_dispatch(TileList<T...>, int block, int vpt, F&& f) {
+    return (... || (block == T::block && vpt == T::vpt && (f(T{}), true)));
+}
+template <class F>
+static bool tile_dispatch(int block, int vpt, F&& f) {
+    return tile_dispatch(TileShapes{}, block, vpt, f);
 }
 
 extern "C" {
@@ -5787,14 +5806,11 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     // the speculative pass leaves them (123.9 vs 126.9 us, profiles/r06j_desc_emit_compact_ab.txt)
     e->desc_emit = 2;
     e->stream_spec = 1;
+    DeviceGuard dev(device);
     {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
         hipError_t h = hipMalloc(&e->ctl, kCtlWords * sizeof(uint32_t));
         if (h == hipSuccess) h = hipMemset(e->ctl, 0, kCtlWords * sizeof(uint32_t));
         if (h == hipSuccess) h = hipDeviceSynchronize();
-        (void)hipSetDevice(prev);
         if (h != hipSuccess) {
             if (e->ctl) (void)hipFree(e->ctl);
             free(e);
@@ -5811,14 +5827,9 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     {
         uint32_t dev_start = 0;
         bool ok = experiment_knobs(e, &dev_start);
-        if (ok && dev_start) {  // (a test's seed of the device epoch)
-            int prev = 0;
-            (void)hipGetDevice(&prev);
-            (void)hipSetDevice(device);
+        if (ok && dev_start)  // (a test's seed of the device epoch)
             ok = hipMemcpy(e->ctl + kCtlEpoch, &dev_start, sizeof(dev_start), hipMemcpyHostToDevice) == hipSuccess &&
                  hipDeviceSynchronize() == hipSuccess;
-            (void)hipSetDevice(prev);
-        }
         if (!ok) {
             (void)hipFree(e->ctl);
             free(e);
@@ -5832,25 +5843,16 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
 
 void uvhttp_ws_gpu_engine_free(uvhttp_ws_gpu_engine_t* e) {
     if (!e) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     (void)hipDeviceSynchronize();
-    scratch_free(e, e->ws_mem);
-    scratch_free(e, e->ss_mem);
-    scratch_free(e, e->bs_mem);
-    scratch_free(e, e->wt_mem);
-    scratch_free(e, e->wr_mem);
-    scratch_free(e, e->dscr);
-    scratch_free(e, e->sp_mem);
-    scratch_free(e, e->u8_mem);
-    scratch_free(e, e->rp_mem);
+    for (const Scratch& b : e->scr) {  // (the device is drained)
+        if (b.p) (void)(e->pool_ok ? hipFreeAsync(b.p, nullptr) : hipFree(b.p));
+    }
     if (e->pool_ok) (void)hipStreamSynchronize(nullptr);
     if (e->ctl) (void)hipFree(e->ctl);
     if (e->stamp_mem) (void)hipFree(e->stamp_mem);
     if (e->order_ev) (void)hipEventDestroy(e->order_ev);
     for (int k = 0; k < e->ev_created; ++k) (void)hipEventDestroy(e->ev[k]);
-    (void)hipSetDevice(prev);
     free(e);
 }
 
@@ -5860,14 +5862,11 @@ const char* uvhttp_ws_gpu_engine_last_error(const uvhttp_ws_gpu_engine_t* e) {
 
 int uvhttp_ws_gpu_engine_sync(uvhttp_ws_gpu_engine_t* e, void* stream) {
     if (!e) return UVHTTP_WS_GPU_EINVAL;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     hipError_t h = hipStreamSynchronize((hipStream_t)stream);
     uint32_t faults = e->faults_seen;
     if (h == hipSuccess)
         h = hipMemcpy(&faults, e->ctl + kCtlFaults, sizeof(faults), hipMemcpyDeviceToHost);
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "sync", h);
     if (faults != e->faults_seen) {
         const uint32_t n = faults - e->faults_seen;
@@ -5893,13 +5892,10 @@ void uvhttp_ws_gpu_test_epoch_limits(uint32_t* max_host_epoch, uint32_t* max_epo
 int uvhttp_ws_gpu_test_engine_epochs(uvhttp_ws_gpu_engine_t* e, void* stream, uint32_t* host_epoch,
                                      uint32_t* device_epoch) {
     if (!e || !host_epoch || !device_epoch) return UVHTTP_WS_GPU_EINVAL;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     hipError_t h = hipStreamSynchronize((hipStream_t)stream);
     if (h == hipSuccess)
         h = hipMemcpy(device_epoch, e->ctl + kCtlEpoch, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (prev != e->device) (void)hipSetDevice(prev);
     if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "epochs", h);
     *host_epoch = e->epoch;
     return UVHTTP_WS_GPU_OK;
@@ -5945,26 +5941,47 @@ static hipError_t scratch_grow(uvhttp_ws_gpu_engine_t* e, void** p, size_t bytes
     }
     return h;
 }
-// an engine-owned scratch block at engine_free (the device is drained first)
-static void scratch_free(uvhttp_ws_gpu_engine_t* e, void* p) {
-    if (!p) return;
-    if (e->pool_ok) (void)hipFreeAsync(p, nullptr);
-    else (void)hipFree(p);
+// The rule by which every engine-owned scratch block grows, stated once.  `fits` (the caller's
+// capacity test): nothing happens.  A captured call must not allocate: refused.  Otherwise the
+// block forgets its capacity and scratch_grow replaces it with one of `bytes`, on the call's
+// stream s (in_call) or from the host (engine_reserve); a failed growth leaves the block empty.
+// The engine's device is current (EngineCall, or engine_reserve's guard).
+enum ScratchRc { kScratchFits, kScratchGrown, kScratchCaptured, kScratchNoMem };
+static ScratchRc scratch_fit(uvhttp_ws_gpu_engine_t* e, Scratch& b, bool fits, size_t bytes, bool zero,
+                             hipStream_t s, bool in_call, hipError_t* why = nullptr) {
+    if (fits) return kScratchFits;
+    if (e->capturing) return kScratchCaptured;
+    b.bytes = 0;
+    const hipError_t h = scratch_grow(e, &b.p, bytes, zero, s, in_call);
+    if (h != hipSuccess) {
+        b.p = nullptr;
+        if (why) *why = h;
+        return kScratchNoMem;
+    }
+    b.bytes = bytes;
+    return kScratchGrown;
+}
+// ... for a block that is only a byte count, inside a call
+static ScratchRc scratch_fit(uvhttp_ws_gpu_engine_t* e, ScratchId id, size_t bytes, bool zero,
+                             hipStream_t s, hipError_t* why = nullptr) {
+    Scratch& b = e->scr[id];
+    return scratch_fit(e, b, b.p && b.bytes >= bytes, bytes, zero, s, true, why);
+}
+// ... not zeroed, as a pointer: null when it cannot grow (captured, or out of memory)
+static void* scratch_ptr(uvhttp_ws_gpu_engine_t* e, ScratchId id, size_t bytes, hipStream_t s) {
+    (void)scratch_fit(e, id, bytes, false, s);
+    return e->scr[id].bytes >= bytes ? e->scr[id].p : nullptr;
 }
 
 // the workspace for max_frames / wire / arena; in_call: grown on the call's stream s
 static int reserve_ws(uvhttp_ws_gpu_engine_t* e, uint32_t max_frames, uint64_t max_wire_bytes,
                       uint64_t max_arena_bytes, hipStream_t s, bool in_call) {
-    if (!e) return UVHTTP_WS_GPU_EINVAL;
     if (max_frames > kMaxFrames) return set_err(e, UVHTTP_WS_GPU_EINVAL, "too many frames", hipSuccess);
     const uint64_t tiles = (max_wire_bytes + kMapTile - 1) / kMapTile + 1;
     const uint64_t atiles = (max_arena_bytes + kMapTile - 1) / kMapTile + 1;
-    if (e->ws_mem && max_frames <= e->cap_frames && tiles <= e->cap_tiles &&
-        atiles <= e->cap_arena_tiles)
-        return UVHTTP_WS_GPU_OK;
-    if (e->capturing)
-        return set_err(e, UVHTTP_WS_GPU_EINVAL, "workspace too small for a captured call: reserve first",
-                       hipSuccess);
+    Scratch& mem = e->scr[kScrWs];
+    const bool fits = mem.p && max_frames <= e->cap_frames && tiles <= e->cap_tiles &&
+                      atiles <= e->cap_arena_tiles;
     const uint32_t fr = max_frames > e->cap_frames ? max_frames : e->cap_frames;
     const uint64_t tl = tiles > e->cap_tiles ? tiles : e->cap_tiles;
     const uint64_t at = atiles > e->cap_arena_tiles ? atiles : e->cap_arena_tiles;
@@ -5984,19 +6001,20 @@ static int reserve_ws(uvhttp_ws_gpu_engine_t* e, uint32_t max_frames, uint64_t m
     size_t off_parts = align_up(off_recs + (size_t)fr * sizeof(FrameRec8), 256);
     size_t off_info = align_up(off_parts + ((size_t)fr / (kBlock * kScanFpt) + 2) * sizeof(TilePart), 256);
     size_t bytes = align_up(off_info + (size_t)fr + 64, 256);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
+    hipError_t h = hipSuccess;
     // zero: ticket counters start at 0 and no flag / tag matches a live epoch (epochs >= 1)
-    hipError_t h = scratch_grow(e, &e->ws_mem, bytes, true, s, in_call);
-    (void)hipSetDevice(prev);
-    if (h != hipSuccess) {
-        e->ws_mem = nullptr;
-        e->cap_frames = 0;
-        e->cap_tiles = e->cap_arena_tiles = 0;
-        return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc workspace", h);
+    switch (scratch_fit(e, mem, fits, bytes, true, s, in_call, &h)) {
+        case kScratchFits: return UVHTTP_WS_GPU_OK;
+        case kScratchCaptured:
+            return set_err(e, UVHTTP_WS_GPU_EINVAL, "workspace too small for a captured call: reserve first",
+                           hipSuccess);
+        case kScratchNoMem:
+            e->cap_frames = 0;
+            e->cap_tiles = e->cap_arena_tiles = 0;
+            return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc workspace", h);
+        case kScratchGrown: break;
     }
-    char* b = (char*)e->ws_mem;
+    char* b = (char*)mem.p;
     e->ws.block_agg = (ScanElem*)(b + off_agg);
     e->ws.group_agg = (ScanElem*)(b + off_grp);
     e->ws.block_incl = (ScanElem*)(b + off_incl);
@@ -6012,7 +6030,6 @@ static int reserve_ws(uvhttp_ws_gpu_engine_t* e, uint32_t max_frames, uint64_t m
     e->ws.parts = b + off_parts;
     e->ws.info = (uint8_t*)(b + off_info);
     e->ws.ctl = e->ctl;
-    e->ws_bytes = bytes;
     e->cap_frames = fr;
     e->cap_tiles = tl;
     e->cap_arena_tiles = at;
@@ -6021,21 +6038,19 @@ static int reserve_ws(uvhttp_ws_gpu_engine_t* e, uint32_t max_frames, uint64_t m
 
 int uvhttp_ws_gpu_engine_reserve(uvhttp_ws_gpu_engine_t* e, uint32_t max_frames,
                                  uint64_t max_wire_bytes, uint64_t max_arena_bytes) {
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    DeviceGuard dev(e->device);  // (outside a call: grown from the host)
     return reserve_ws(e, max_frames, max_wire_bytes, max_arena_bytes, nullptr, false);
 }
 
 int uvhttp_ws_gpu_engine_set_tile(uvhttp_ws_gpu_engine_t* e, int block, int vectors_per_lane) {
     if (!e) return UVHTTP_WS_GPU_EINVAL;
-    static const int ok[][2] = {{0, 0}, {64, 1}, {64, 2}, {64, 4}, {128, 1},
-                                {128, 2}, {256, 1}, {256, 2}, {256, 4}};
-    for (const auto& c : ok) {
-        if (c[0] == block && c[1] == vectors_per_lane) {
-            e->tile_block = block;
-            e->tile_vpt = vectors_per_lane;
-            return UVHTTP_WS_GPU_OK;
-        }
-    }
-    return set_err(e, UVHTTP_WS_GPU_EINVAL, "unsupported tile shape", hipSuccess);
+    // 0 x 0: automatic
+    if (!(block == 0 && vectors_per_lane == 0) && !tile_dispatch(block, vectors_per_lane, [](auto) {}))
+        return set_err(e, UVHTTP_WS_GPU_EINVAL, "unsupported tile shape", hipSuccess);
+    e->tile_block = block;
+    e->tile_vpt = vectors_per_lane;
+    return UVHTTP_WS_GPU_OK;
 }
 
 int uvhttp_ws_gpu_engine_set_timing(uvhttp_ws_gpu_engine_t* e, int enable) {
@@ -6060,11 +6075,10 @@ static void harvest(uvhttp_ws_gpu_engine_t* e) {
 
 int uvhttp_ws_gpu_engine_kernel_time(uvhttp_ws_gpu_engine_t* e, double* ms, uint64_t* launches) {
     if (!e) return UVHTTP_WS_GPU_EINVAL;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
-    harvest(e);
-    (void)hipSetDevice(prev);
+    {
+        DeviceGuard dev(e->device);
+        harvest(e);
+    }
     if (ms) *ms = e->time_ms;
     if (launches) *launches = e->launches;
     e->time_ms = 0;
@@ -6075,13 +6089,10 @@ int uvhttp_ws_gpu_engine_kernel_time(uvhttp_ws_gpu_engine_t* e, double* ms, uint
 int uvhttp_ws_gpu_engine_set_stamps(uvhttp_ws_gpu_engine_t* e, int enable) {
     if (!e) return UVHTTP_WS_GPU_EINVAL;
     if (enable && !e->stamp_mem) {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(e->device);
+        DeviceGuard dev(e->device);
         hipError_t h = hipMalloc(&e->stamp_mem, kStampWords * 8);
         if (h == hipSuccess) h = hipMemset(e->stamp_mem, 0, kStampWords * 8);
         if (h == hipSuccess) h = hipDeviceSynchronize();
-        (void)hipSetDevice(prev);
         if (h != hipSuccess) {
             if (e->stamp_mem) (void)hipFree(e->stamp_mem);
             e->stamp_mem = nullptr;
@@ -6099,16 +6110,14 @@ int uvhttp_ws_gpu_engine_read_stamps(uvhttp_ws_gpu_engine_t* e, uvhttp_ws_gpu_st
     if (!e->stamp_mem) return UVHTTP_WS_GPU_OK;
     uint64_t* host = (uint64_t*)malloc(kStampWords * 8);
     if (!host) return UVHTTP_WS_GPU_ENOMEM;
-    int prev = 0, khz = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
+    int khz = 0;
+    DeviceGuard dev(e->device);
     hipError_t h = hipDeviceSynchronize();
     if (h == hipSuccess) h = hipMemcpy(host, e->stamp_mem, kStampWords * 8, hipMemcpyDeviceToHost);
     if (h == hipSuccess) h = hipMemset(e->stamp_mem, 0, kStampWords * 8);
     if (h == hipSuccess) h = hipDeviceSynchronize();
     if (h == hipSuccess && hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, e->device) != hipSuccess)
         khz = 0;
-    (void)hipSetDevice(prev);
     if (h != hipSuccess) {
         free(host);
         return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "read stamps", h);
@@ -6239,11 +6248,13 @@ static void timing_end(uvhttp_ws_gpu_engine_t* e, int k, hipStream_t s) {
 // tagged items, block by block: DESIGN.md, "Epoch-tagged state".  Every block is a multiple of
 // 8 bytes (256-byte aligned sizes; BuildRec is 64 bytes).
 static EpochClear epoch_blocks(const uvhttp_ws_gpu_engine_t* e) {
+    // (the other blocks carry no tags and are not cleared: the walk slices can be 16 GiB)
+    static const ScratchId tagged[4] = {kScrWs, kScrBs, kScrSp, kScrSs};
     EpochClear c;
-    c.p[0] = (uint64_t*)e->ws_mem, c.n[0] = e->ws_mem ? e->ws_bytes / 8 : 0;
-    c.p[1] = (uint64_t*)e->bs_mem, c.n[1] = e->bs_mem ? e->bs_tiles * sizeof(BuildRec) / 8 : 0;
-    c.p[2] = (uint64_t*)e->sp_mem, c.n[2] = e->sp_mem ? e->sp_bytes / 8 : 0;
-    c.p[3] = (uint64_t*)e->ss_mem, c.n[3] = e->ss_mem ? e->ss_bytes / 8 : 0;
+    for (int m = 0; m < 4; ++m) {
+        const Scratch& b = e->scr[tagged[m]];
+        c.p[m] = (uint64_t*)b.p, c.n[m] = b.bytes / 8;
+    }
     return c;
 }
 
@@ -6268,12 +6279,6 @@ static uint32_t next_epoch(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
     return ++e->epoch;
 }
 
-// scope of one API call: call_begin decides capture mode; leaving the call clears it
-struct CallScope {
-    uvhttp_ws_gpu_engine_t* e;
-    ~CallScope() { e->capturing = 0; }
-};
-
 // Start of every call: is the stream being captured, and does the call switch streams?  The
 // engine's workspace serves one call at a time, so a call on a new stream first waits for
 // what the previous call's stream has queued.
@@ -6291,21 +6296,33 @@ static void call_begin(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
     e->have_last = 1;
 }
 
-// ws_engine_int.h: the same call frame for sources outside this file (utf8_gpu.hip)
+// The frame of one API call that queues work: the engine's device is made current first, then
+// call_begin runs, so everything the call does (scratch growth included) happens on that device;
+// leaving the scope, by any return, leaves capture mode and restores the caller's device.
+struct EngineCall {
+    uvhttp_ws_gpu_engine_t* e;
+    DeviceGuard dev;
+    EngineCall(uvhttp_ws_gpu_engine_t* eng, hipStream_t s) : e(eng), dev(eng->device) { call_begin(e, s); }
+    // the second half of a call that uvws_call_enter began
+    EngineCall(uvhttp_ws_gpu_engine_t* eng, int prev_device) : e(eng), dev(eng->device, prev_device) {}
+    ~EngineCall() { e->capturing = 0; }
+    // the call's result once its work is queued: a pending launch error -> ELAUNCH, last_error set
+    int finish(const char* what = "launch") {
+        const hipError_t h = hipGetLastError();
+        return h == hipSuccess ? UVHTTP_WS_GPU_OK : set_err(e, UVHTTP_WS_GPU_ELAUNCH, what, h);
+    }
+};
+
+// ws_engine_int.h: the same call frame, in two halves, for sources outside this file
 int uvws_call_enter(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    DeviceGuard dev(e->device);
     call_begin(e, s);
-    return prev;
+    return dev.keep();  // (the call goes on: uvws_call_leave ends it)
 }
 
 int uvws_call_leave(uvhttp_ws_gpu_engine_t* e, int prev_device, const char* what) {
-    e->capturing = 0;
-    const hipError_t h = hipGetLastError();
-    if (prev_device != e->device) (void)hipSetDevice(prev_device);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, what, h);
-    return UVHTTP_WS_GPU_OK;
+    EngineCall call(e, prev_device);
+    return call.finish(what);
 }
 
 int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what) {
@@ -6390,46 +6407,21 @@ static uint64_t max_payload_in(uint64_t slot, int32_t is_server) {
     return best;
 }
 
-// the engine's descriptor scratch for calls that pass d_desc == NULL on a path that needs
-// descriptors internally (grown on demand; a captured call must not grow it)
-static uvhttp_ws_frame_desc_t* desc_scratch(uvhttp_ws_gpu_engine_t* e, uint32_t n, hipStream_t s) {
-    const uint64_t want = n ? n : 1;
-    if (e->dscr && e->dscr_cap >= want) return e->dscr;
-    if (e->capturing) return nullptr;
-    e->dscr_cap = 0;
-    if (scratch_grow(e, reinterpret_cast<void**>(&e->dscr), want * sizeof(uvhttp_ws_frame_desc_t),
-                     false, s, true) != hipSuccess) {
-        e->dscr = nullptr;
-        return nullptr;
-    }
-    e->dscr_cap = want;
-    return e->dscr;
+// a call that passes d_desc == NULL on a path that needs descriptors internally gets the engine's
+// descriptor scratch (grown on demand; a captured call must not grow it)
+static int own_desc(uvhttp_ws_gpu_engine_t* e, uvhttp_ws_frame_desc_t** d_desc, uint32_t n, hipStream_t s) {
+    if (*d_desc) return UVHTTP_WS_GPU_OK;
+    *d_desc = (uvhttp_ws_frame_desc_t*)scratch_ptr(e, kScrDesc, (n ? n : 1) * sizeof(uvhttp_ws_frame_desc_t), s);
+    if (*d_desc) return UVHTTP_WS_GPU_OK;
+    return set_err(e, UVHTTP_WS_GPU_ENOMEM, "descriptor scratch (reserve before capturing)", hipSuccess);
 }
 
-// ws_engine_int.h: the frame UTF-8 validator's scratch, by the same rule
+// ws_engine_int.h: the frame UTF-8 validator's scratch and the control replies'
 void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
-    if (e->u8_mem && e->u8_bytes >= bytes) return e->u8_mem;
-    if (e->capturing) return nullptr;
-    e->u8_bytes = 0;
-    if (scratch_grow(e, &e->u8_mem, bytes, false, s, true) != hipSuccess) {
-        e->u8_mem = nullptr;
-        return nullptr;
-    }
-    e->u8_bytes = bytes;
-    return e->u8_mem;
+    return scratch_ptr(e, kScrUtf8, bytes, s);
 }
-
-// ... and the control replies' (ws_replies_gpu.hip)
 void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
-    if (e->rp_mem && e->rp_bytes >= bytes) return e->rp_mem;
-    if (e->capturing) return nullptr;
-    e->rp_bytes = 0;
-    if (scratch_grow(e, &e->rp_mem, bytes, false, s, true) != hipSuccess) {
-        e->rp_mem = nullptr;
-        return nullptr;
-    }
-    e->rp_bytes = bytes;
-    return e->rp_mem;
+    return scratch_ptr(e, kScrReplies, bytes, s);
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot
@@ -6458,24 +6450,238 @@ static int check_batch(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b,
     return UVHTTP_WS_GPU_OK;
 }
 
+// blocks of k_sum_scan and of the kernels that consume its TileParts
+static uint32_t sum_parts(uint32_t n) { return (n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt); }
+
+// run_decode's three paths.  Each queues its kernels on s and returns OK, or an error with
+// last_error set; run_decode checks the launches.
+
+// stride batches in place: the fused path (payload pass parses the headers, k_plan runs
+// on its records, k_fixup undoes what a failure must leave untouched)
+static int decode_fused(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, BatchArgs& a,
+                        uvhttp_ws_frame_desc_t* d_desc, uvhttp_ws_message_desc_t* d_msgs, hipStream_t s) {
+    a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
+    a.stride_inv = 1.0 / (double)b->frame_stride;
+    // 16 KiB tiles at every fused frame size: the tile's LDS staging, parse and barriers
+    // are paid per tile, so the fused pass wants larger tiles than the plain payload
+    // kernel (r03p34: 256x4 97.9 us on C4, 256x2 112.6, 64x1 182.7; r03p35: 32 KiB tiles
+    // lose, 256x8 +16 %, 512x4 +5 %); an explicit shape (set_tile) holds here too
+    int fb = e->tile_block, fv = e->tile_vpt;
+    if (!fb) {
+        fb = 256;
+        fv = 4;
+    }
+    const uint64_t ft = (uint64_t)fb * fv * 16;
+    const uint64_t f_tiles = (b->wire_len + ft - 1) / ft;
+    // Summary-only decode (d_desc == NULL): the payload pass also runs the fragment state
+    // machine (the previous frame decides it when every frame before a delivered one is a
+    // data frame — stride >= kSumMinStride — and no message can reach max_message_size: the
+    // bound below) and leaves one TilePart per tile; k_sum_tail writes the summary and undoes
+    // a failure.  No records, no k_plan, no descriptors.
+    const bool sum_fast = !d_desc && fb == 256 && fv == 4 && sum_ok(e, b);
+    // descriptors under the same bounds: records + info bytes, the info-byte scan, then the
+    // parallel descriptor pass (k_desc_emit) instead of k_plan on the records + k_fixup
+    const bool desc_emit = d_desc && e->desc_emit && fb == 256 && fv == 4 && sum_ok(e, b);
+    const uint32_t n_parts = sum_parts(a.n);
+    if (desc_emit) {
+        // (desc_emit >= 2: no info bytes — the scan and k_desc_emit rebuild them from the records)
+        const bool from_rec = e->desc_emit >= 2;
+        const int stk = timing_begin(e, s);
+        for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+            if (from_rec)
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveRec>), dim3(grid_p), dim3(256), 0, s, a,
+                                   e->ws, tb);
+            else
+                hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveBoth>), dim3(grid_p), dim3(256), 0, s, a,
+                                   e->ws, tb);
+        });
+        timing_end(e, stk, s);
+        if (from_rec) {
+            hipLaunchKernelGGL((k_sum_scan<false, UVHTTP_WS_STAMP_SUM_SCAN, true>), dim3(n_parts), dim3(kBlock),
+                               0, s, a, e->ws);
+            hipLaunchKernelGGL(k_desc_emit<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_desc);
+        } else {
+            BatchArgs ai = a;  // the scan reads the info bytes
+            ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
+            hipLaunchKernelGGL((k_sum_scan<false, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0,
+                               s, ai, e->ws);
+            hipLaunchKernelGGL(k_desc_emit<false>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_desc);
+        }
+        return UVHTTP_WS_GPU_OK;
+    }
+    if (sum_fast) {
+        // (a.recs: the info bytes, 1 per frame)
+        const int stk = timing_begin(e, s);
+        for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+            hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveInfo>), dim3(grid_p), dim3(256), 0, s, a,
+                               e->ws, tb);
+        });
+        timing_end(e, stk, s);
+        hipLaunchKernelGGL(k_sum_scan<false>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws);
+        hipLaunchKernelGGL(k_sum_tail, dim3(kSumTailGrid), dim3(kBlock), 0, s, a, e->ws, n_parts);
+        return UVHTTP_WS_GPU_OK;
+    }
+    if (const int rc = own_desc(e, &d_desc, a.n, s)) return rc;
+    const int ftk = timing_begin(e, s);
+    bool known = true;  // (the shapes set_tile accepts)
+    for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+        known = known && tile_dispatch(fb, fv, [&](auto t) {
+            constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
+            hipLaunchKernelGGL((k_unmask_stride<B, V>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);
+        });
+    });
+    if (!known) return set_err(e, UVHTTP_WS_GPU_EINVAL, "unsupported fused tile shape", hipSuccess);
+    timing_end(e, ftk, s);
+    if (e->rec_lookback) {
+        launch_plan(e, a, a.n, d_desc, d_msgs, s);
+    } else {
+        constexpr int kRecFpt = 4;
+        a.plan_frames = kBlock * kRecFpt;
+        const uint32_t nblk = (a.n + a.plan_frames - 1) / a.plan_frames;
+        hipLaunchKernelGGL(k_rec_reduce<kRecFpt>, dim3(nblk), dim3(kBlock), 0, s, a, e->ws);
+        hipLaunchKernelGGL(k_rec_scan, dim3(1), dim3(kScanBlock), 0, s, e->ws, nblk);
+        hipLaunchKernelGGL(k_rec_resolve<kRecFpt>, dim3(nblk), dim3(kBlock), 0, s, a, d_desc,
+                           d_msgs, e->ws);
+    }
+    const uint32_t fx = (a.n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_fixup, dim3(fx < kFixupBlocks ? fx : kFixupBlocks), dim3(kBlock), 0, s, a, d_desc,
+                       e->ws);
+    return UVHTTP_WS_GPU_OK;
+}
+
+// compact stride batches of small frames, speculatively: the payload pass
+// parses the headers (records) and writes every uniform frame's payload to f * P right
+// away; k_plan on the records checks that every delivered frame is where it went, and
+// k_spec_fix redoes the batch with the full scatter when one is not.  spec_p: the uniform
+// payload length; no_desc: d_desc is the engine's scratch, the caller wants the summary only
+static int decode_spec(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, BatchArgs& a, uint64_t spec_p,
+                       bool no_desc, uvhttp_ws_frame_desc_t* d_desc, uvhttp_ws_message_desc_t* d_msgs,
+                       hipStream_t s) {
+    a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
+    a.stride_inv = 1.0 / (double)b->frame_stride;
+    a.spec_P = spec_p;
+    constexpr uint64_t kSt = 256ull * 4 * 16;
+    const uint64_t s_tiles = (b->wire_len + kSt - 1) / kSt;
+    // summary-only (d_desc == NULL): the pass leaves info bytes instead of records;
+    // k_sum_scan / k_sum_tail / k_sum_msgs run the state machine, check the speculation and
+    // write the summary and the message table; a batch that broke the speculation (a control
+    // frame, another length, ...) is decoded again by k_plan + k_spec_fix, which otherwise
+    // return at once (ctl[kCtlGate])
+    const bool sum_c = no_desc && sum_ok(e, b) && a.arena_cap / spec_p >= a.n;
+    // with descriptors under the same bounds: the pass leaves records and info bytes, the
+    // scan reads the info bytes, k_sum_msgs also writes the descriptors from the records
+    const bool desc_c = !no_desc && e->desc_emit && sum_ok(e, b) && a.arena_cap / spec_p >= a.n;
+    // (sum_c: a.recs holds the info bytes)
+    const int stk = timing_begin(e, s);
+    for_grid_chunks(s_tiles, [&](uint32_t grid_s, uint64_t tb) {
+        if (desc_c)
+            hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveBoth>), dim3(grid_s), dim3(256), 0,
+                               s, a, e->ws, tb);
+        else if (sum_c)
+            hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveInfo>), dim3(grid_s), dim3(256), 0, s, a,
+                               e->ws, tb);
+        else
+            hipLaunchKernelGGL((k_unmask_stride<256, 4, true>), dim3(grid_s), dim3(256), 0, s, a, e->ws, tb);
+    });
+    timing_end(e, stk, s);
+    const uint32_t n_parts = sum_parts(a.n);
+    if (sum_c) {
+        hipLaunchKernelGGL(k_sum_scan<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws);
+        hipLaunchKernelGGL(k_sum_msgs<>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_msgs,
+                           nullptr);
+        a.recs = nullptr;  // the fallback's k_plan gathers the headers
+        a.gate = 1;
+    } else if (desc_c) {
+        BatchArgs ai = a;  // the scan reads the info bytes
+        ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
+        hipLaunchKernelGGL((k_sum_scan<true, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0, s, ai,
+                           e->ws);
+        hipLaunchKernelGGL(k_sum_msgs<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_msgs,
+                           d_desc);
+        a.gate = 1;  // (the fall-back's k_plan reads the same records)
+    }
+    launch_plan(e, a, a.n, d_desc, d_msgs, s);
+    // (gated — it returns at once unless the speculation failed — a smaller grid: the
+    // no-op launch costs less, the rare fall-back strides over more frames per block)
+    const uint32_t nblk = (a.n + kBlock - 1) / kBlock;
+    const uint32_t fix_max = a.gate ? 256u : 1024u;
+    hipLaunchKernelGGL(k_spec_fix, dim3(nblk < fix_max ? nblk : fix_max), dim3(kBlock), 0, s, a, d_desc,
+                       e->ws, s_tiles);
+    return UVHTTP_WS_GPU_OK;
+}
+
+// every other batch: k_plan on the wire's headers, then the payload kernel (in place, or the
+// compact scatter / gather into a.arena)
+static int decode_planned(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, BatchArgs& a,
+                          uvhttp_ws_frame_desc_t* d_desc, uvhttp_ws_message_desc_t* d_msgs, hipStream_t s) {
+    const uint8_t* arena = a.arena;
+    launch_plan(e, a, a.n, d_desc, d_msgs, s);
+    // payload kernel tile shape: explicit (set_tile) or by average wire bytes per frame
+    // (auto shapes from tools/tile_sweep.py on MI355X, profiles/r01_tile_sweep.txt)
+    int blk = e->tile_block, vpt = e->tile_vpt;
+    const uint64_t avg = a.n ? b->wire_len / a.n : 0;
+    // compact decode: frames below kScatterAvg wire bytes on average take the wire-driven
+    // scatter kernel, larger ones the arena-driven gather (UVHTTP_WS_COMPACT=gather|scatter)
+    const bool scatter = arena && (e->compact_mode ? e->compact_mode == 2 : avg < kScatterAvg);
+    if (!blk) {
+        if (!arena) {
+            inplace_tile_shape(avg, blk, vpt);
+        } else if (scatter) {
+            blk = avg >= 32768 ? 64 : 256;
+            vpt = avg >= 32768 ? 1 : avg >= 2048 ? 2 : 4;
+            // the scatter kernel wants 16 KiB tiles at 2-16 KiB frames too (C2 compact 86.2 ->
+            // 84.3 us, profiles/r04_tile_ab.txt)
+            if (avg >= 2048 && avg < 16384) vpt = 4;
+        } else {
+            blk = avg >= 2048 ? 64 : 256;
+            vpt = 2;
+        }
+    }
+    const uint64_t span = arena && !scatter ? a.n_arena_tiles * kMapTile : b->wire_len;
+    const uint64_t tile_bytes = (uint64_t)blk * vpt * 16;
+    uint64_t n_ptiles = (span + tile_bytes - 1) / tile_bytes;
+    // in place and wire-driven compact: the payload kernel's first ceil(n / blk) blocks also
+    // finalize (no k_finalize launch; not over an empty wire: its tile loads would have no
+    // buffer to read)
+    const bool fold_fin = b->wire_len != 0 && (!arena || scatter);
+    const uint64_t n_fin = (a.n + blk - 1) / blk;
+    if (fold_fin && n_ptiles < n_fin) n_ptiles = n_fin;
+    const int tk = timing_begin(e, s);
+    for_grid_chunks(a.n ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
+        (void)tile_dispatch(blk, vpt, [&](auto t) {
+            constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
+            if (!arena)
+                hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws, tb);
+            else if (scatter)
+                hipLaunchKernelGGL((k_scatter_compact<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws,
+                                   a.arena_cap, tb);
+            else
+                hipLaunchKernelGGL((k_gather_compact<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws,
+                                   a.arena_cap, tb);
+        });
+    });
+    timing_end(e, tk, s);
+    if (!fold_fin || !a.n) {
+        const uint32_t grid_fin = a.n ? (a.n + kBlock - 1) / kBlock : 1;
+        hipLaunchKernelGGL(k_finalize, dim3(grid_fin), dim3(kBlock), 0, s, a, d_desc, e->ws);
+    }
+    return UVHTTP_WS_GPU_OK;
+}
+
 static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uint8_t* arena,
                       uint64_t arena_cap, uvhttp_ws_frame_desc_t* d_desc,
                       uvhttp_ws_message_desc_t* d_msgs, uvhttp_ws_batch_summary_t* d_summary,
                       void* stream) {
     int rc = check_batch(e, b, d_summary);
     if (rc) return rc;
-    CallScope scope{e};
-    call_begin(e, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    EngineCall call(e, s);
     const uint64_t n_tiles = (b->wire_len + kMapTile - 1) / kMapTile;
     // arena tiles: bounded by both the capacity and the data payload that can exist
     uint64_t arena_need = arena ? (arena_cap < b->wire_len ? arena_cap : b->wire_len) : 0;
     const uint64_t n_atiles = arena ? (arena_need + kMapTile - 1) / kMapTile : 0;
-    rc = reserve_ws(e, b->n_frames, b->wire_len, arena_need, (hipStream_t)stream, true);
+    rc = reserve_ws(e, b->n_frames, b->wire_len, arena_need, s, true);
     if (rc) return rc;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
-    hipStream_t s = (hipStream_t)stream;
 
     BatchArgs a;
     memset(&a, 0, sizeof(a));  // stream-mode fields stay null in batch mode
@@ -6499,260 +6705,25 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
     a.stamp = (e->stamp_on && !e->capturing) ? e->stamp_mem : nullptr;
     a.cas_claims = e->captured_ever ? 1u : 0u;
 
-    // stride batches in place: the fused path (payload pass parses the headers, k_plan runs
-    // on its records, k_fixup undoes what a failure must leave untouched)
-    const bool fused = !arena && !b->frame_off && !e->fused_off && a.n > 0 &&
-                       b->wire_len / a.n <= e->fused_max_avg &&
-                       b->frame_stride >= kFusedMinStride && b->wire_len > 0 &&
-                       b->wire_len < (1ull << 52) &&
-                       (uint64_t)(a.n - 1) <= (b->wire_len - 1) / b->frame_stride;
-    if (fused) {
-        a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
-        a.stride_inv = 1.0 / (double)b->frame_stride;
-        // 16 KiB tiles at every fused frame size: the tile's LDS staging, parse and barriers
-        // are paid per tile, so the fused pass wants larger tiles than the plain payload
-        // kernel (r03p34: 256x4 97.9 us on C4, 256x2 112.6, 64x1 182.7; r03p35: 32 KiB tiles
-        // lose, 256x8 +16 %, 512x4 +5 %); an explicit shape (set_tile) holds here too
-        int fb = e->tile_block, fv = e->tile_vpt;
-        if (!fb) {
-            fb = 256;
-            fv = 4;
-        }
-        const uint64_t ft = (uint64_t)fb * fv * 16;
-        const uint64_t f_tiles = (b->wire_len + ft - 1) / ft;
-        const uint64_t f_max = (1ull << 24);
-        // Summary-only decode (d_desc == NULL): the payload pass also runs the fragment state
-        // machine (the previous frame decides it when every frame before a delivered one is a
-        // data frame — stride >= kSumMinStride — and no message can reach max_message_size: the
-        // bound below) and leaves one TilePart per tile; k_sum_tail writes the summary and undoes
-        // a failure.  No records, no k_plan, no descriptors.
-        const bool sum_fast = !d_desc && fb == 256 && fv == 4 && sum_ok(e, b);
-        // descriptors under the same bounds: records + info bytes, the info-byte scan, then the
-        // parallel descriptor pass (k_desc_emit) instead of k_plan on the records + k_fixup
-        const bool desc_emit = d_desc && e->desc_emit && fb == 256 && fv == 4 && sum_ok(e, b);
-        if (desc_emit) {
-            // (desc_emit >= 2: no info bytes — the scan and k_desc_emit rebuild them from the records)
-            const bool from_rec = e->desc_emit >= 2;
-            const int stk = timing_begin(e, s);
-            for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
-                const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
-                if (from_rec)
-                    hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveRec>), dim3(grid_p), dim3(256), 0, s, a,
-                                       e->ws, tb);
-                else
-                    hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveBoth>), dim3(grid_p), dim3(256), 0, s, a,
-                                       e->ws, tb);
-            }
-            timing_end(e, stk, s);
-            const uint32_t n_parts = (a.n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt);
-            if (from_rec) {
-                hipLaunchKernelGGL((k_sum_scan<false, UVHTTP_WS_STAMP_SUM_SCAN, true>), dim3(n_parts), dim3(kBlock),
-                                   0, s, a, e->ws);
-                hipLaunchKernelGGL(k_desc_emit<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_desc);
-            } else {
-                BatchArgs ai = a;  // the scan reads the info bytes
-                ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
-                hipLaunchKernelGGL((k_sum_scan<false, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0,
-                                   s, ai, e->ws);
-                hipLaunchKernelGGL(k_desc_emit<false>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_desc);
-            }
-            hipError_t hs = hipGetLastError();
-            if (prev != e->device) (void)hipSetDevice(prev);
-            if (hs != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hs);
-            return UVHTTP_WS_GPU_OK;
-        }
-        if (sum_fast) {
-            a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);  // (the info bytes: 1 per frame)
-            const int stk = timing_begin(e, s);
-            for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
-                const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveInfo>), dim3(grid_p), dim3(256), 0, s, a,
-                                   e->ws, tb);
-            }
-            timing_end(e, stk, s);
-            const uint32_t n_parts = (a.n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt);
-            hipLaunchKernelGGL(k_sum_scan<false>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws);
-            hipLaunchKernelGGL(k_sum_tail, dim3(kSumTailGrid), dim3(kBlock), 0, s, a, e->ws, n_parts);
-            hipError_t hs = hipGetLastError();
-            if (prev != e->device) (void)hipSetDevice(prev);
-            if (hs != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hs);
-            return UVHTTP_WS_GPU_OK;
-        }
-        if (!d_desc && !(d_desc = desc_scratch(e, a.n, s))) {
-            if (prev != e->device) (void)hipSetDevice(prev);
-            return set_err(e, UVHTTP_WS_GPU_ENOMEM, "descriptor scratch (reserve before capturing)", hipSuccess);
-        }
-        const int ftk = timing_begin(e, s);
-        for (uint64_t tb = 0; tb < f_tiles; tb += f_max) {
-            const uint32_t grid_p = (uint32_t)((f_tiles - tb) < f_max ? (f_tiles - tb) : f_max);
-#define UVWS_FUSED(B, V)                                                                         \
-    if (fb == B && fv == V)                                                                      \
-        hipLaunchKernelGGL((k_unmask_stride<B, V>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);  \
-    else
-            // (the shapes set_tile accepts)
-            UVWS_FUSED(64, 1) UVWS_FUSED(64, 2) UVWS_FUSED(64, 4) UVWS_FUSED(128, 1)
-            UVWS_FUSED(128, 2) UVWS_FUSED(256, 1) UVWS_FUSED(256, 2) UVWS_FUSED(256, 4) {
-                if (prev != e->device) (void)hipSetDevice(prev);
-                return set_err(e, UVHTTP_WS_GPU_EINVAL, "unsupported fused tile shape", hipSuccess);
-            }
-#undef UVWS_FUSED
-        }
-        timing_end(e, ftk, s);
-        if (e->rec_lookback) {
-            launch_plan(e, a, a.n, d_desc, d_msgs, s);
-        } else {
-            constexpr int kRecFpt = 4;
-            a.plan_frames = kBlock * kRecFpt;
-            const uint32_t nblk = (a.n + a.plan_frames - 1) / a.plan_frames;
-            hipLaunchKernelGGL(k_rec_reduce<kRecFpt>, dim3(nblk), dim3(kBlock), 0, s, a, e->ws);
-            hipLaunchKernelGGL(k_rec_scan, dim3(1), dim3(kScanBlock), 0, s, e->ws, nblk);
-            hipLaunchKernelGGL(k_rec_resolve<kRecFpt>, dim3(nblk), dim3(kBlock), 0, s, a, d_desc,
-                               d_msgs, e->ws);
-        }
-        const uint32_t fx = (a.n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_fixup, dim3(fx < kFixupBlocks ? fx : kFixupBlocks), dim3(kBlock), 0, s, a, d_desc,
-                           e->ws);
-        hipError_t hf = hipGetLastError();
-        if (prev != e->device) (void)hipSetDevice(prev);
-        if (hf != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hf);
-        return UVHTTP_WS_GPU_OK;
+    // what the two stride-batch paths share: a stride batch whose frames all start inside the wire
+    const bool strided = !b->frame_off && a.n > 0 && b->frame_stride >= kFusedMinStride &&
+                         b->wire_len > 0 && b->wire_len < (1ull << 52) &&
+                         (uint64_t)(a.n - 1) <= (b->wire_len - 1) / b->frame_stride;
+    if (!arena && strided && !e->fused_off && b->wire_len / a.n <= e->fused_max_avg) {
+        rc = decode_fused(e, b, a, d_desc, d_msgs, s);
+    } else {
+        // every other path keeps per-frame descriptors internally: a caller without them gets the
+        // engine's scratch
+        const bool no_desc = !d_desc;
+        if ((rc = own_desc(e, &d_desc, a.n, s))) return rc;
+        const uint64_t spec_p = spec_payload(b->frame_stride);
+        if (arena && strided && e->spec_on && spec_p && b->wire_len / a.n <= e->spec_max_avg &&
+            e->compact_mode != 1 && arena_cap < (1ull << 52))
+            rc = decode_spec(e, b, a, spec_p, no_desc, d_desc, d_msgs, s);
+        else
+            rc = decode_planned(e, b, a, d_desc, d_msgs, s);
     }
-    // every other path keeps per-frame descriptors internally: a caller without them gets the
-    // engine's scratch
-    const bool no_desc = !d_desc;
-    if (!d_desc && !(d_desc = desc_scratch(e, a.n, s))) {
-        if (prev != e->device) (void)hipSetDevice(prev);
-        return set_err(e, UVHTTP_WS_GPU_ENOMEM, "descriptor scratch (reserve before capturing)", hipSuccess);
-    }
-    // compact stride batches of small frames, speculatively: the payload pass
-    // parses the headers (records) and writes every uniform frame's payload to f * P right
-    // away; k_plan on the records checks that every delivered frame is where it went, and
-    // k_spec_fix redoes the batch with the full scatter when one is not
-    const uint64_t spec_p = spec_payload(b->frame_stride);
-    const bool spec = arena && !b->frame_off && e->spec_on && a.n > 0 && spec_p &&
-                      b->wire_len / a.n <= e->spec_max_avg && e->compact_mode != 1 &&
-                      b->frame_stride >= kFusedMinStride && b->wire_len > 0 &&
-                      b->wire_len < (1ull << 52) && arena_cap < (1ull << 52) &&
-                      (uint64_t)(a.n - 1) <= (b->wire_len - 1) / b->frame_stride;
-    if (spec) {
-        a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);
-        a.stride_inv = 1.0 / (double)b->frame_stride;
-        a.spec_P = spec_p;
-        constexpr uint64_t kSt = 256ull * 4 * 16;
-        const uint64_t s_tiles = (b->wire_len + kSt - 1) / kSt;
-        // summary-only (d_desc == NULL): the pass leaves info bytes instead of records;
-        // k_sum_scan / k_sum_tail / k_sum_msgs run the state machine, check the speculation and
-        // write the summary and the message table; a batch that broke the speculation (a control
-        // frame, another length, ...) is decoded again by k_plan + k_spec_fix, which otherwise
-        // return at once (ctl[kCtlGate])
-        const bool sum_c = no_desc && sum_ok(e, b) && arena_cap / spec_p >= a.n;
-        // with descriptors under the same bounds: the pass leaves records and info bytes, the
-        // scan reads the info bytes, k_sum_msgs also writes the descriptors from the records
-        const bool desc_c = !no_desc && e->desc_emit && sum_ok(e, b) && arena_cap / spec_p >= a.n;
-        if (sum_c) a.recs = reinterpret_cast<FrameRec8*>(e->ws.recs);  // (the info bytes)
-        const int stk = timing_begin(e, s);
-        for (uint64_t tb = 0; tb < s_tiles; tb += (1ull << 24)) {
-            const uint32_t grid_s = (uint32_t)((s_tiles - tb) < (1ull << 24) ? (s_tiles - tb) : (1ull << 24));
-            if (desc_c)
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveBoth>), dim3(grid_s), dim3(256), 0,
-                                   s, a, e->ws, tb);
-            else if (sum_c)
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveInfo>), dim3(grid_s), dim3(256), 0, s, a,
-                                   e->ws, tb);
-            else
-                hipLaunchKernelGGL((k_unmask_stride<256, 4, true>), dim3(grid_s), dim3(256), 0, s, a, e->ws, tb);
-        }
-        timing_end(e, stk, s);
-        if (sum_c) {
-            const uint32_t n_parts = (a.n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt);
-            hipLaunchKernelGGL(k_sum_scan<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws);
-            hipLaunchKernelGGL(k_sum_msgs<>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_msgs,
-                               nullptr);
-            a.recs = nullptr;  // the fallback's k_plan gathers the headers
-            a.gate = 1;
-        } else if (desc_c) {
-            const uint32_t n_parts = (a.n + kBlock * kScanFpt - 1) / (kBlock * kScanFpt);
-            BatchArgs ai = a;  // the scan reads the info bytes
-            ai.recs = reinterpret_cast<FrameRec8*>(e->ws.info);
-            hipLaunchKernelGGL((k_sum_scan<true, UVHTTP_WS_STAMP_SUM_SCAN>), dim3(n_parts), dim3(kBlock), 0, s, ai,
-                               e->ws);
-            hipLaunchKernelGGL(k_sum_msgs<true>, dim3(n_parts), dim3(kBlock), 0, s, a, e->ws, n_parts, d_msgs,
-                               d_desc);
-            a.gate = 1;  // (the fall-back's k_plan reads the same records)
-        }
-        launch_plan(e, a, a.n, d_desc, d_msgs, s);
-        // (gated — it returns at once unless the speculation failed — a smaller grid: the
-        // no-op launch costs less, the rare fall-back strides over more frames per block)
-        const uint32_t nblk = (a.n + kBlock - 1) / kBlock;
-        const uint32_t fix_max = a.gate ? 256u : 1024u;
-        hipLaunchKernelGGL(k_spec_fix, dim3(nblk < fix_max ? nblk : fix_max), dim3(kBlock), 0, s, a, d_desc,
-                           e->ws, s_tiles);
-        const hipError_t hs = hipGetLastError();
-        if (prev != e->device) (void)hipSetDevice(prev);
-        if (hs != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hs);
-        return UVHTTP_WS_GPU_OK;
-    }
-    launch_plan(e, a, a.n, d_desc, d_msgs, s);
-    // payload kernel tile shape: explicit (set_tile) or by average wire bytes per frame
-    // (auto shapes from tools/tile_sweep.py on MI355X, profiles/r01_tile_sweep.txt)
-    int blk = e->tile_block, vpt = e->tile_vpt;
-    const uint64_t avg = a.n ? b->wire_len / a.n : 0;
-    // compact decode: frames below kScatterAvg wire bytes on average take the wire-driven
-    // scatter kernel, larger ones the arena-driven gather (UVHTTP_WS_COMPACT=gather|scatter)
-    const bool scatter = arena && (e->compact_mode ? e->compact_mode == 2 : avg < kScatterAvg);
-    if (!blk) {
-        if (!arena) {
-            inplace_tile_shape(avg, blk, vpt);
-        } else if (scatter) {
-            blk = avg >= 32768 ? 64 : 256;
-            vpt = avg >= 32768 ? 1 : avg >= 2048 ? 2 : 4;
-            // the scatter kernel wants 16 KiB tiles at 2-16 KiB frames too (C2 compact 86.2 ->
-            // 84.3 us, profiles/r04_tile_ab.txt)
-            if (avg >= 2048 && avg < 16384) vpt = 4;
-        } else {
-            blk = avg >= 2048 ? 64 : 256;
-            vpt = 2;
-        }
-    }
-    const uint64_t span = arena && !scatter ? n_atiles * kMapTile : b->wire_len;
-    const uint64_t tile_bytes = (uint64_t)blk * vpt * 16;
-    uint64_t n_ptiles = (span + tile_bytes - 1) / tile_bytes;
-    // in place and wire-driven compact: the payload kernel's first ceil(n / blk) blocks also
-    // finalize (no k_finalize launch; not over an empty wire: its tile loads would have no
-    // buffer to read)
-    const bool fold_fin = b->wire_len != 0 && (!arena || scatter);
-    const uint64_t n_fin = (a.n + blk - 1) / blk;
-    if (fold_fin && n_ptiles < n_fin) n_ptiles = n_fin;
-    // the dispatch packet counts work-items in 32 bits: split very large passes
-    const uint64_t max_tiles = (1ull << 24);
-    const int tk = timing_begin(e, s);
-    for (uint64_t tb = 0; a.n && tb < n_ptiles; tb += max_tiles) {
-        const uint32_t grid_p = (uint32_t)((n_ptiles - tb) < max_tiles ? (n_ptiles - tb) : max_tiles);
-#define UVWS_LAUNCH(B, V)                                                                        \
-    if (blk == B && vpt == V) {                                                                  \
-        if (!arena)                                                                              \
-            hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, \
-                               e->ws, tb);                                                       \
-        else if (scatter)                                                                        \
-            hipLaunchKernelGGL((k_scatter_compact<B, V>), dim3(grid_p), dim3(B), 0, s, a,        \
-                               d_desc, e->ws, arena_cap, tb);                                    \
-        else                                                                                     \
-            hipLaunchKernelGGL((k_gather_compact<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, \
-                               e->ws, arena_cap, tb);                                            \
-    } else
-        UVWS_LAUNCH(64, 1) UVWS_LAUNCH(64, 2) UVWS_LAUNCH(64, 4) UVWS_LAUNCH(128, 1)
-        UVWS_LAUNCH(128, 2) UVWS_LAUNCH(256, 1) UVWS_LAUNCH(256, 2) UVWS_LAUNCH(256, 4) {}
-#undef UVWS_LAUNCH
-    }
-    timing_end(e, tk, s);
-    if (!fold_fin || !a.n) {
-        const uint32_t grid_fin = a.n ? (a.n + kBlock - 1) / kBlock : 1;
-        hipLaunchKernelGGL(k_finalize, dim3(grid_fin), dim3(kBlock), 0, s, a, d_desc, e->ws);
-    }
-    hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_WS_GPU_OK;
+    return rc ? rc : call.finish();
 }
 
 int uvhttp_ws_gpu_decode_inplace(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b,
@@ -6778,10 +6749,8 @@ static int reserve_streams(uvhttp_ws_gpu_engine_t* e, uint32_t frames, uint32_t 
     // the connection count of a call never reallocates: a caller such as the batcher issues a
     // call while its previous one still runs on the stream)
     (void)streams;
-    if (e->ss_mem && frames <= e->ss_frames && reads <= e->ss_reads) return UVHTTP_WS_GPU_OK;
-    if (e->capturing)
-        return set_err(e, UVHTTP_WS_GPU_EINVAL, "stream scratch too small for a captured call",
-                       hipSuccess);
+    Scratch& mem = e->scr[kScrSs];
+    const bool fits = mem.p && frames <= e->ss_frames && reads <= e->ss_reads;
     const uint32_t fr = frames > e->ss_frames ? frames : e->ss_frames;
     const uint32_t rd = reads > e->ss_reads ? reads : e->ss_reads;
     size_t o_off = 0;
@@ -6791,22 +6760,21 @@ static int reserve_streams(uvhttp_ws_gpu_engine_t* e, uint32_t frames, uint32_t 
     size_t o_ctr = align_up(o_agg + ((size_t)kMaxFrames / kBlock + 2) * 4, 256);
     size_t o_srec = align_up(o_ctr + 16, 256);
     size_t bytes = align_up(o_srec + (size_t)kSwalkFusedMaxBlocks * 32, 256);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
+    hipError_t h = hipSuccess;
     // (zero: the counters start at 0 and no record tag matches a live epoch.  On the call's
     // stream: a call of this engine may still run there with the old block — the batcher issues
     // a call while its previous one runs — and releases it first; scratch_grow)
-    hipError_t h = scratch_grow(e, &e->ss_mem, bytes, true, s, true);
-    (void)hipSetDevice(prev);
-    if (h != hipSuccess) {
-        e->ss_mem = nullptr;
-        e->ss_frames = e->ss_reads = 0;
-        e->ss_bytes = 0;
-        return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc stream scratch", h);
+    switch (scratch_fit(e, mem, fits, bytes, true, s, true, &h)) {
+        case kScratchFits: return UVHTTP_WS_GPU_OK;
+        case kScratchCaptured:
+            return set_err(e, UVHTTP_WS_GPU_EINVAL, "stream scratch too small for a captured call",
+                           hipSuccess);
+        case kScratchNoMem:
+            e->ss_frames = e->ss_reads = 0;
+            return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc stream scratch", h);
+        case kScratchGrown: break;
     }
-    e->ss_bytes = bytes;
-    char* b = (char*)e->ss_mem;
+    char* b = (char*)mem.p;
     e->ss.frame_off = (uint64_t*)(b + o_off);
     e->ss.n_total = (uint32_t*)(b + o_tot);
     e->ss.read_size = (uint64_t*)(b + o_rsize);
@@ -6818,7 +6786,7 @@ static int reserve_streams(uvhttp_ws_gpu_engine_t* e, uint32_t frames, uint32_t 
     return UVHTTP_WS_GPU_OK;
 }
 
-// The layout of the speculative stream decode's scratch (sp_mem) for `streams` connections and
+// The layout of the speculative stream decode's scratch (kScrSp) for `streams` connections and
 // `tiles` kSpecT-byte wire tiles: the one place its offsets are computed (reserve_spec sizes the
 // block from it, the decode fills SpecArgs from it with the reserved capacities).
 struct SpecLayout {
@@ -6843,27 +6811,23 @@ static SpecLayout spec_layout(uint32_t streams, uint64_t tiles) {
 
 // the speculative stream decode's scratch (zeroed: no tile claim matches a live epoch)
 static int reserve_spec(uvhttp_ws_gpu_engine_t* e, uint32_t streams, uint64_t tiles, hipStream_t s) {
-    if (e->sp_mem && streams <= e->sp_streams && tiles <= e->sp_tiles) return UVHTTP_WS_GPU_OK;
-    if (e->capturing)
-        return set_err(e, UVHTTP_WS_GPU_EINVAL, "stream scratch too small for a captured call", hipSuccess);
+    Scratch& mem = e->scr[kScrSp];
+    const bool fits = mem.p && streams <= e->sp_streams && tiles <= e->sp_tiles;
     const uint32_t ns = streams > e->sp_streams ? streams : e->sp_streams;
     const uint64_t nt = tiles > e->sp_tiles ? tiles : e->sp_tiles;
-    const size_t bytes = spec_layout(ns, nt).bytes;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e->device);
-    const hipError_t h = scratch_grow(e, &e->sp_mem, bytes, true, s, true);
-    (void)hipSetDevice(prev);
-    if (h != hipSuccess) {
-        e->sp_mem = nullptr;
-        e->sp_streams = 0;
-        e->sp_tiles = 0;
-        e->sp_bytes = 0;
-        return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc speculative stream scratch", h);
+    hipError_t h = hipSuccess;
+    switch (scratch_fit(e, mem, fits, spec_layout(ns, nt).bytes, true, s, true, &h)) {
+        case kScratchFits: return UVHTTP_WS_GPU_OK;
+        case kScratchCaptured:
+            return set_err(e, UVHTTP_WS_GPU_EINVAL, "stream scratch too small for a captured call", hipSuccess);
+        case kScratchNoMem:
+            e->sp_streams = 0;
+            e->sp_tiles = 0;
+            return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc speculative stream scratch", h);
+        case kScratchGrown: break;
     }
     e->sp_streams = ns;
     e->sp_tiles = nt;
-    e->sp_bytes = bytes;
     return UVHTTP_WS_GPU_OK;
 }
 
@@ -6892,16 +6856,12 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     if (max_frames > kMaxFrames || n_streams > kMaxFrames)
         return set_err(e, UVHTTP_WS_GPU_EINVAL, "too many frames/streams", hipSuccess);
     if (!n_streams) return UVHTTP_WS_GPU_OK;
-    CallScope scope{e};
-    call_begin(e, (hipStream_t)stream);
-    const uint32_t cap = max_frames ? max_frames : 1;
-    int rc = reserve_ws(e, cap, wire_len, 0, (hipStream_t)stream, true);
-    if (!rc) rc = reserve_streams(e, cap, n_streams, n_reads_total, (hipStream_t)stream);
-    if (rc) return rc;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
+    EngineCall call(e, s);
+    const uint32_t cap = max_frames ? max_frames : 1;
+    int rc = reserve_ws(e, cap, wire_len, 0, s, true);
+    if (!rc) rc = reserve_streams(e, cap, n_streams, n_reads_total, s);
+    if (rc) return rc;
 
     // a wave per connection when the waves fill the chip in about one round, else a lane
     // (UVHTTP_WS_WALK=lane|wave pins it).  (Behind a speculative attempt, below, the walk path is
@@ -6919,18 +6879,14 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     // (up to 16 GiB of slices — twice the wire, on a 288 GB device: C3's 4.3 GB streams call
     // walks in one pass; above 8 GiB it walked twice, the second walk + scan ~1 % of its step)
     const uint64_t want = wire_len / 2 + n_streams + 1;
-    if (single_ok && !e->capturing && want * 4 <= (16ull << 30) && want > e->wt_cap) {
-        // (an earlier call may still use the slices: released behind it on the stream)
-        e->wt_cap = 0;
-        if (scratch_grow(e, &e->wt_mem, want * 4, false, s, true) == hipSuccess) e->wt_cap = want;
-    }
+    // (an earlier call may still use the slices: released behind it on the stream.  A captured
+    // call, or one out of memory, goes without: it walks twice)
+    if (single_ok && want * 4 <= (16ull << 30)) (void)scratch_fit(e, kScrWt, want * 4, false, s);
     // the wave walk's frame records (8 bytes per slice entry) while slices and records stay
     // within 8 GiB together; larger calls gather every header again in k_stream_desc
     // (only the wave walk writes and reads them: none for the lane walk — 1 GB less for C2)
-    if (single_ok && wave_walk && !e->capturing && want * 12 <= (8ull << 30) && want > e->wr_cap) {
-        e->wr_cap = 0;
-        if (scratch_grow(e, &e->wr_mem, want * 8, false, s, true) == hipSuccess) e->wr_cap = want;
-    }
+    if (single_ok && wave_walk && want * 12 <= (8ull << 30)) (void)scratch_fit(e, kScrWr, want * 8, false, s);
+    const Scratch &wt = e->scr[kScrWt], &wr = e->scr[kScrWr];
     WalkArgs w;
     w.wire = d_wire;
     w.wire_len = wire_len;
@@ -6939,7 +6895,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     w.max_frames = max_frames;
     w.read_end = d_read_end;
     w.n_reads_total = n_reads_total;
-    w.single = (single_ok && e->wt_cap >= want) ? 1u : 0u;
+    w.single = (single_ok && wt.bytes / 4 >= want) ? 1u : 0u;
     w.results = d_results;
     w.desc = d_desc;
     w.tile_first = e->ws.tile_first;
@@ -6948,8 +6904,8 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     w.dev_epoch = e->capturing ? 1u : 0u;
     w.epoch = next_epoch(e, s);
     w.sc = e->ss;
-    w.sc.walk_tmp = (uint32_t*)e->wt_mem;
-    w.sc.walk_rec = (w.single && e->wr_cap >= want && e->wr_rec_on) ? (uint2*)e->wr_mem : nullptr;
+    w.sc.walk_tmp = (uint32_t*)wt.p;
+    w.sc.walk_rec = (w.single && wr.bytes / 8 >= want && e->wr_rec_on) ? (uint2*)wr.p : nullptr;
     w.agg = e->ss.agg;
     w.stamp = (e->stamp_on && !e->capturing) ? e->stamp_mem : nullptr;
     w.cas_claims = e->captured_ever ? 1u : 0u;
@@ -6975,7 +6931,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
         sa.max_frames = max_frames;
         sa.read_end = d_read_end;
         sa.n_reads_total = n_reads_total;
-        char* sb = (char*)e->sp_mem;
+        char* sb = (char*)e->scr[kScrSp].p;
         const SpecLayout sl = spec_layout(e->sp_streams, e->sp_tiles);
         sa.conns = (SpecConn*)(sb + sl.conns);
         sa.blk = (uint32_t*)(sb + sl.blk);
@@ -6995,10 +6951,9 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
         hipLaunchKernelGGL(k_sspec_plan, dim3(nsb), dim3(kBlock), 0, s, sa);
         hipLaunchKernelGGL(k_sspec_tiles, dim3((uint32_t)((sp_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sa);
         tk_spec = timing_begin(e, s);
-        for (uint64_t tb = 0; tb < sp_tiles; tb += (1ull << 24)) {
-            const uint32_t g = (uint32_t)((sp_tiles - tb) < (1ull << 24) ? (sp_tiles - tb) : (1ull << 24));
+        for_grid_chunks(sp_tiles, [&](uint32_t g, uint64_t tb) {
             hipLaunchKernelGGL(k_sspec_pass, dim3(g), dim3(kBlock), 0, s, sa, tb);
-        }
+        });
         timing_end(e, tk_spec, s);
         hipLaunchKernelGGL(k_sspec_emit, dim3(nwb), dim3(kBlock), 0, s, sa);
         w.spec = 1;
@@ -7065,10 +7020,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
         const uint32_t g = sp_tiles < kSpecUndoGrid ? (uint32_t)sp_tiles : kSpecUndoGrid;
         hipLaunchKernelGGL(k_sspec_fallback, dim3(g), dim3(kBlock), 0, s, sa_keep, a, d_desc, e->ws, sp_tiles);
         timing_end(e, tk_chain, s);
-        const hipError_t hs = hipGetLastError();
-        if (prev != e->device) (void)hipSetDevice(prev);
-        if (hs != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", hs);
-        return UVHTTP_WS_GPU_OK;
+        return call.finish();
     }
     // payload tile shape: the frame count is only known on the device, so the caller's frame
     // capacity stands in for it (wire bytes per frame slot; the same rule as the batch decode)
@@ -7079,24 +7031,16 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     }
     const uint64_t tile_bytes = (uint64_t)blk * vpt * 16;
     const uint64_t n_ptiles = (wire_len + tile_bytes - 1) / tile_bytes;
-    const uint64_t max_tiles = (1ull << 24);
     const int tk = e->time_chain ? -1 : timing_begin(e, s);
-    for (uint64_t tb = 0; tb < n_ptiles; tb += max_tiles) {
-        const uint32_t grid_p = (uint32_t)((n_ptiles - tb) < max_tiles ? (n_ptiles - tb) : max_tiles);
-#define UVWS_LAUNCH(B, V)                                                                        \
-    if (blk == B && vpt == V)                                                                    \
-        hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws, tb); \
-    else
-        UVWS_LAUNCH(64, 1) UVWS_LAUNCH(64, 2) UVWS_LAUNCH(64, 4) UVWS_LAUNCH(128, 1)
-        UVWS_LAUNCH(128, 2) UVWS_LAUNCH(256, 1) UVWS_LAUNCH(256, 2) UVWS_LAUNCH(256, 4) {}
-#undef UVWS_LAUNCH
-    }
+    for_grid_chunks(n_ptiles, [&](uint32_t grid_p, uint64_t tb) {
+        (void)tile_dispatch(blk, vpt, [&](auto t) {
+            constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
+            hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws, tb);
+        });
+    });
     timing_end(e, tk, s);
     timing_end(e, tk_chain, s);
-    const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_WS_GPU_OK;
+    return call.finish();
 }
 
 int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, uint64_t src_len,
@@ -7109,15 +7053,11 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, 
     if (((uintptr_t)d_out) & 15u)
         return set_err(e, UVHTTP_WS_GPU_EINVAL, "out must be 16-byte aligned", hipSuccess);
     if (n_frames > kMaxFrames) return set_err(e, UVHTTP_WS_GPU_EINVAL, "too many frames", hipSuccess);
-    CallScope scope{e};
-    call_begin(e, (hipStream_t)stream);
-    // scratch: reuse the engine workspace (block/group aggregates as u64, arena map)
-    int rc = reserve_ws(e, n_frames ? n_frames : 1, 0, 0, (hipStream_t)stream, true);
-    if (rc) return rc;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
+    EngineCall call(e, s);
+    // scratch: reuse the engine workspace (block/group aggregates as u64, arena map)
+    int rc = reserve_ws(e, n_frames ? n_frames : 1, 0, 0, s, true);
+    if (rc) return rc;
     BuildArgs b;
     b.group = kEmitF;
     b.src = d_src;
@@ -7146,24 +7086,16 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, 
     while (shift < 16 && (2ull << shift) <= avg) ++shift;
     b.map_shift = shift;
     b.n_map = grouped ? 0 : (out_cap + (1ull << shift) - 1) >> shift;  // grouped: no map records
-    if (!grouped && b.n_map + 1 > e->bs_tiles) {
-        if (e->capturing) {
-            if (prev != e->device) (void)hipSetDevice(prev);
-            return set_err(e, UVHTTP_WS_GPU_EINVAL, "build map too small for a captured call",
-                           hipSuccess);
-        }
-        e->bs_tiles = 0;
+    if (!grouped) {
+        hipError_t h = hipSuccess;
         // + 1: kb_emit reads the record after its tile's; that spare entry is never tagged.
         // zero: tag 0 never matches a live epoch (epochs >= 1)
-        hipError_t h = scratch_grow(e, &e->bs_mem, (b.n_map + 1) * sizeof(BuildRec), true, s, true);
-        if (h != hipSuccess) {
-            e->bs_mem = nullptr;
-            if (prev != e->device) (void)hipSetDevice(prev);
-            return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc build map", h);
-        }
-        e->bs_tiles = b.n_map + 1;
+        const ScratchRc g = scratch_fit(e, kScrBs, (b.n_map + 1) * sizeof(BuildRec), true, s, &h);
+        if (g == kScratchCaptured)
+            return set_err(e, UVHTTP_WS_GPU_EINVAL, "build map too small for a captured call", hipSuccess);
+        if (g == kScratchNoMem) return set_err(e, UVHTTP_WS_GPU_ENOMEM, "hipMalloc build map", h);
     }
-    b.mrec = reinterpret_cast<BuildRec*>(e->bs_mem);
+    b.mrec = reinterpret_cast<BuildRec*>(e->scr[kScrBs].p);
     b.ctl = e->ctl;
     b.dev_epoch = e->capturing ? 1u : 0u;
     b.epoch = next_epoch(e, s);
@@ -7182,9 +7114,7 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, 
         hipLaunchKernelGGL(kb_scan_groups, dim3(n_groups), dim3(kBlock), 0, s, b, grid_f);
         hipLaunchKernelGGL(kb_scan_top, dim3(1), dim3(kBlock), 0, s, b, n_groups);
     }
-    const uint64_t avg0 = n_frames ? out_cap / n_frames : out_cap;
-    if (!(n_frames && avg0 < e->build_frames_max))
-        hipLaunchKernelGGL(kb_offsets, dim3(grid_f), dim3(kBlock), 0, s, b, n_groups);
+    if (!grouped) hipLaunchKernelGGL(kb_offsets, dim3(grid_f), dim3(kBlock), 0, s, b, n_groups);
     if (!n_frames) {
         // d_out_off[0] = 0 (total) for an empty batch
         (void)hipMemsetAsync(d_out_off, 0, 8, s);
@@ -7212,10 +7142,7 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, 
     else if (sh == 1) launch_emit<64, 4>(b, n_frames, out_cap, s);
     else launch_emit<64, 2>(b, n_frames, out_cap, s);
     timing_end(e, tk, s);
-    const hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_WS_GPU_OK;
+    return call.finish();
 }
 
 int uvhttp_ws_gpu_apply_mask(uvhttp_ws_gpu_engine_t* e, uint8_t* d_data, uint64_t len,
@@ -7229,23 +7156,14 @@ int uvhttp_ws_gpu_apply_mask(uvhttp_ws_gpu_engine_t* e, uint8_t* d_data, uint64_
     const uint64_t nvec = (len - head) / 16;
     uint64_t tiles = (nvec + kMaskBlock - 1) / kMaskBlock;
     if (tiles < 1) tiles = 1;  // tile 0 also does the head and tail bytes
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
     hipStream_t s = (hipStream_t)stream;
-    CallScope scope{e};
-    call_begin(e, s);
+    EngineCall call(e, s);
     const int tk = timing_begin(e, s);
-    const uint64_t max_tiles = (1ull << 24);
-    for (uint64_t tb = 0; tb < tiles; tb += max_tiles) {
-        const uint32_t grid = (uint32_t)((tiles - tb) < max_tiles ? (tiles - tb) : max_tiles);
+    for_grid_chunks(tiles, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_apply_mask, dim3(grid), dim3(kMaskBlock), 0, s, d_data, len, k, head, tb);
-    }
+    });
     timing_end(e, tk, s);
-    hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_WS_GPU_OK;
+    return call.finish();
 }
 
 int uvhttp_ws_gpu_gen_frames(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint32_t n_frames,
@@ -7266,16 +7184,11 @@ int uvhttp_ws_gpu_gen_frames_range(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, u
     uint64_t total = (uint64_t)count * wpf;
     uint64_t grid = (total + kBlock - 1) / kBlock;
     if (grid > 65536) grid = 65536;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != e->device) (void)hipSetDevice(e->device);
+    EngineCall call(e, (hipStream_t)stream);
     hipLaunchKernelGGL(k_gen_frames, dim3((uint32_t)grid), dim3(kBlock), 0, (hipStream_t)stream,
                        d_wire, first, count, n_frames, payload_len, seed, opcode0, fragmented,
                        force_keys, wpf);
-    hipError_t h = hipGetLastError();
-    if (prev != e->device) (void)hipSetDevice(prev);
-    if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_WS_GPU_OK;
+    return call.finish();
 }
 
 // ---- host-memory pipeline ----------------------------------------------------------------
@@ -7328,9 +7241,7 @@ constexpr int kPipeInFlight = 3;
 
 void uvhttp_ws_gpu_pipeline_free(uvhttp_ws_gpu_pipeline_t* p) {
     if (!p) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    DeviceGuard dev(p->device);
     if (p->up) (void)hipStreamSynchronize(p->up);
     if (p->cs) (void)hipStreamSynchronize(p->cs);
     for (int k = 0; k < p->depth && p->slots; ++k) {
@@ -7354,7 +7265,6 @@ void uvhttp_ws_gpu_pipeline_free(uvhttp_ws_gpu_pipeline_t* p) {
     if (p->cs) (void)hipStreamDestroy(p->cs);
     uvhttp_ws_gpu_engine_free(p->eng);
     free(p->slots);
-    (void)hipSetDevice(prev);
     free(p);
 }
 
@@ -7379,9 +7289,7 @@ int uvhttp_ws_gpu_pipeline_create(int device, int depth, uint64_t slot_bytes,
     }
     int rc = uvhttp_ws_gpu_engine_create(device, &p->eng);
     if (!rc) rc = uvhttp_ws_gpu_engine_reserve(p->eng, slot_frames, slot_bytes, 0);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
+    DeviceGuard dev(device);
     if (!rc && (hipStreamCreateWithFlags(&p->up, hipStreamNonBlocking) != hipSuccess ||
                 hipStreamCreateWithFlags(&p->cs, hipStreamNonBlocking) != hipSuccess))
         rc = UVHTTP_WS_GPU_ENOMEM;
@@ -7403,7 +7311,6 @@ int uvhttp_ws_gpu_pipeline_create(int device, int depth, uint64_t slot_bytes,
             hipEventCreateWithFlags(&s.done_ev, hipEventDisableTiming) != hipSuccess)
             rc = UVHTTP_WS_GPU_ENOMEM;
     }
-    (void)hipSetDevice(prev);
     if (rc) {
         uvhttp_ws_gpu_pipeline_free(p);
         return rc;
@@ -7427,9 +7334,7 @@ int uvhttp_ws_gpu_pipeline_submit(uvhttp_ws_gpu_pipeline_t* p, int slot, uint64_
     if (!p || slot < 0 || slot >= p->depth) return UVHTTP_WS_GPU_EINVAL;
     PipeSlot& s = p->slots[slot];
     if (s.busy || wire_len > p->slot_bytes || n_frames > p->slot_frames) return UVHTTP_WS_GPU_EINVAL;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    DeviceGuard dev(p->device);
     // upload stream: the slot's bytes (its previous round was waited for, so d_wire is free)
     hipError_t h = hipSuccess;
     // at most in_flight submissions queued: wait for the one in_flight submissions back (its
@@ -7470,7 +7375,6 @@ int uvhttp_ws_gpu_pipeline_submit(uvhttp_ws_gpu_pipeline_t* p, int slot, uint64_
         p->recent[p->n_sub % 16] = slot;
         p->n_sub++;
     }
-    (void)hipSetDevice(prev);
     return rc;
 }
 
@@ -7486,9 +7390,7 @@ int uvhttp_ws_gpu_pipeline_submit_compact(uvhttp_ws_gpu_pipeline_t* p, int slot,
     if (!p || slot < 0 || slot >= p->depth) return UVHTTP_WS_GPU_EINVAL;
     PipeSlot& s = p->slots[slot];
     if (s.busy || wire_len > p->slot_bytes || n_frames > p->slot_frames) return UVHTTP_WS_GPU_EINVAL;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    DeviceGuard dev(p->device);
     hipError_t h = hipSuccess;
     const size_t arena_cap = (size_t)p->slot_bytes + 64;
     const size_t msg_bytes = (size_t)p->slot_frames * sizeof(uvhttp_ws_message_desc_t);
@@ -7504,7 +7406,6 @@ int uvhttp_ws_gpu_pipeline_submit_compact(uvhttp_ws_gpu_pipeline_t* p, int slot,
             s.h_msgs = nullptr;
             s.d_msgs = nullptr;
             s.d_arena = nullptr;
-            (void)hipSetDevice(prev);
             return UVHTTP_WS_GPU_ENOMEM;
         }
     }
@@ -7558,7 +7459,6 @@ int uvhttp_ws_gpu_pipeline_submit_compact(uvhttp_ws_gpu_pipeline_t* p, int slot,
         p->recent[p->n_sub % 16] = slot;
         p->n_sub++;
     }
-    (void)hipSetDevice(prev);
     return rc;
 }
 
