@@ -306,7 +306,7 @@ EXPERIMENT_KNOBS = (
     "UVHTTP_WS_SUMMARY_FAST", "UVHTTP_WS_TILE", "UVHTTP_WS_TIMING_FENCE", "UVHTTP_WS_PIPE_IN_FLIGHT",
     "UVHTTP_TLS_CRYPT_GRID", "UVHTTP_WS_BATCHER_TRACE", "UVHTTP_WS_BATCHER_FAIL_EVERY",
     "UVHTTP_WS_COPY_SSE2", "UVHTTP_WS_DESC_EMIT", "UVHTTP_WS_STREAM_SPEC",
-    "UVHTTP_WS_EPOCH_PERIOD", "UVHTTP_WS_DEV_EPOCH_START")
+    "UVHTTP_WS_EPOCH_PERIOD", "UVHTTP_WS_DEV_EPOCH_START", "UVHTTP_WS_GRID_PIECE")
 
 
 def experiment_knobs_set():
@@ -468,6 +468,9 @@ def load_library(path: str) -> C.CDLL:
     hooks = {
         "uvhttp_ws_gpu_test_epoch_limits": (None, [C.POINTER(u32), C.POINTER(u32)]),
         "uvhttp_ws_gpu_test_engine_epochs": (C.c_int, [vp, vp, C.POINTER(u32), C.POINTER(u32)]),
+        "uvhttp_ws_gpu_test_grid_pieces": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "uvhttp_ws_gpu_test_grid_chunks": (u64, [u64, u64, vp, vp, u64]),
+        "uvhttp_ws_gpu_test_max_grid": (u64, []),
     }
     for name, (res, args) in hooks.items():
         if hasattr(L, name):
@@ -483,6 +486,20 @@ def epoch_limits():
     mh, me = C.c_uint32(0), C.c_uint32(0)
     test_hooks_library().uvhttp_ws_gpu_test_epoch_limits(C.byref(mh), C.byref(me))
     return mh.value, me.value
+
+
+def max_grid() -> int:
+    """kMaxGrid (ws_engine_int.h): the most workgroups one launch of a chunked pass gets, and the
+    largest UVHTTP_WS_GRID_PIECE.  From the experiment build; needs no GPU."""
+    return int(test_hooks_library().uvhttp_ws_gpu_test_max_grid())
+
+
+def grid_chunks(piece: int, tiles: int, cap: int = 64):
+    """for_grid_chunks(piece, tiles, ...) run on the host: (number of launches, the first `cap`
+    (grid, tile_base) pairs).  From the experiment build; needs no GPU."""
+    grids, bases = (C.c_uint32 * cap)(), (C.c_uint64 * cap)()
+    n = int(test_hooks_library().uvhttp_ws_gpu_test_grid_chunks(piece, tiles, grids, bases, cap))
+    return n, [(int(grids[k]), int(bases[k])) for k in range(min(n, cap))]
 
 
 def gen_frame_stride(payload_len: int) -> int:
@@ -717,6 +734,18 @@ class GpuEngine:
         self._check(self._L.uvhttp_ws_gpu_test_engine_epochs(self.h, self._stream(stream),
                                                              C.byref(he), C.byref(de)), "epochs")
         return he.value, de.value
+
+    def grid_pieces(self):
+        """(passes, pieces, tiles): the chunked passes this engine's calls queued since the
+        previous read, the launches they took and the workgroups they covered (a pass goes out in
+        launches of at most 2^24 workgroups, or UVHTTP_WS_GRID_PIECE).  A test hook of the
+        experiment build, so that a test can assert its calls really ran in several pieces."""
+        if not hasattr(self._L, "uvhttp_ws_gpu_test_grid_pieces"):
+            raise GpuError("grid_pieces(): only the experiment build has this test hook")
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.uvhttp_ws_gpu_test_grid_pieces(self.h, C.byref(a), C.byref(b), C.byref(c)),
+                    "grid_pieces")
+        return a.value, b.value, c.value
 
     def set_tile(self, block: int, vectors_per_lane: int):
         self._check(self._L.uvhttp_ws_gpu_engine_set_tile(self.h, block, vectors_per_lane),

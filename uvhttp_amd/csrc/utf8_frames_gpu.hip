@@ -651,7 +651,7 @@ int fu_run(uvhttp_ws_gpu_engine_t* e, FuArgs a, void* stream, const char* what) 
         hipLaunchKernelGGL((k_fu_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg2, blocks);
         hipLaunchKernelGGL(k_fu_segs, dim3(blocks), dim3(kBlock), 0, s, a);
         const uint64_t tiles = (a.wire_len + kTileBytes - 1) / kTileBytes;
-        for_grid_chunks(tiles, [&](uint32_t grid, uint64_t tb) {
+        engine_grid_chunks(e, tiles, [&](uint32_t grid, uint64_t tb) {
             hipLaunchKernelGGL(k_fu_tiles, dim3(grid), dim3(kBlock), 0, s, a, tb, blocks);
         });
     }

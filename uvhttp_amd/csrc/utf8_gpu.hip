@@ -370,7 +370,7 @@ extern "C" int uvhttp_ws_gpu_validate_utf8(uvhttp_ws_gpu_engine_t* e, const uint
     const uint32_t grid_n = (uint32_t)(n_cap ? (n_cap + kBlock - 1) / kBlock : 1);
     hipLaunchKernelGGL(k_utf8_init, dim3(grid_n), dim3(kBlock), 0, s, a);
     const uint64_t tiles = (data_len + kTileBytes - 1) / kTileBytes;
-    for_grid_chunks(n_cap ? tiles : 0, [&](uint32_t grid, uint64_t tb) {
+    engine_grid_chunks(e, n_cap ? tiles : 0, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_utf8_tiles, dim3(grid), dim3(kBlock), 0, s, a, tb);
     });
     const uint64_t per_f = (uint64_t)kBlock * kFinishPer;

@@ -5660,6 +5660,10 @@ struct uvhttp_ws_gpu_engine {
     int ev_used;       // event pairs recorded and not yet harvested
     double time_ms;
     uint64_t launches;
+    uint64_t grid_piece;       // workgroups per launch of a chunked pass (for_grid_chunks): kMaxGrid
+#ifdef UVWS_EXPERIMENTS
+    uint64_t gp_passes, gp_pieces, gp_tiles;  // chunked passes since the last read (test hook)
+#endif
     char err[256];
 };
 
@@ -5669,10 +5673,10 @@ static int set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what, hipErr
 }
 
 template <int BLOCK, int VPT>
-static void launch_emit(const BuildArgs& b, uint32_t n_frames, uint64_t out_cap, hipStream_t s) {
+static void launch_emit(uvhttp_ws_gpu_engine_t* e, const BuildArgs& b, uint32_t n_frames, uint64_t out_cap, hipStream_t s) {
     const uint64_t tile_bytes = (uint64_t)BLOCK * VPT * 16;
     const uint64_t n_ptiles = (out_cap + tile_bytes - 1) / tile_bytes;
-    for_grid_chunks(n_frames ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
+    engine_grid_chunks(e, n_frames ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
         hipLaunchKernelGGL((kb_emit<BLOCK, VPT>), dim3(grid_p), dim3(BLOCK), 0, s, b, tb);
     });
 }
@@ -5748,6 +5752,10 @@ static bool experiment_knobs(uvhttp_ws_gpu_engine_t* e, uint32_t* dev_epoch_star
     if (set) e->epoch = v;
     if (!epoch_knob("UVHTTP_WS_DEV_EPOCH_START", (uint64_t)kMaxHostEpoch + 1, kMaxEpoch, &set, &v)) return false;
     *dev_epoch_start = set ? v : 0;
+    // UVHTTP_WS_GRID_PIECE=N (tests/test_gpu_grid_pieces.py): a chunked pass goes out in launches
+    // of at most N workgroups, so small shapes run tile_base != 0 in every kernel that takes one
+    if (!epoch_knob("UVHTTP_WS_GRID_PIECE", 1, kMaxGrid, &set, &v)) return false;
+    if (set) e->grid_piece = v;
     if (const char* bs = getenv("UVHTTP_WS_BUILD_SMALL")) e->build_small = atoi(bs);
     if (const char* fu = getenv("UVHTTP_WS_FUSED")) e->fused_off = atoi(fu) == 0;
     if (const char* fm = getenv("UVHTTP_WS_FUSED_MAX")) e->fused_max_avg = strtoull(fm, nullptr, 10);
@@ -5791,6 +5799,7 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     // the product configuration (each choice measured: DESIGN.md §4-5)
     e->max_polls = kMaxPolls;
     e->epoch_max = kMaxHostEpoch;
+    e->grid_piece = kMaxGrid;
     e->fused_max_avg = kFusedMaxAvg;
     // the fused path scans its records with k_plan's look-back (C4: 133-136 us per step against
     // 144-145 for reduce-then-scan, profiles/r03p6_*)
@@ -5899,6 +5908,38 @@ int uvhttp_ws_gpu_test_engine_epochs(uvhttp_ws_gpu_engine_t* e, void* stream, ui
     if (h != hipSuccess) return set_err(e, UVHTTP_WS_GPU_ELAUNCH, "epochs", h);
     *host_epoch = e->epoch;
     return UVHTTP_WS_GPU_OK;
+}
+
+// The chunked passes (for_grid_chunks) of the engine's calls since the previous read: how many
+// passes launched anything, the launches (pieces) they took and the workgroups (tiles) they
+// covered, so a test can assert that its calls really ran in the pieces it meant.  Host
+// counters of queued launches: a captured call counts when it is captured, not when replayed.
+int uvhttp_ws_gpu_test_grid_pieces(uvhttp_ws_gpu_engine_t* e, uint64_t* passes, uint64_t* pieces,
+                                   uint64_t* tiles) {
+    if (!e || !passes || !pieces || !tiles) return UVHTTP_WS_GPU_EINVAL;
+    *passes = e->gp_passes;
+    *pieces = e->gp_pieces;
+    *tiles = e->gp_tiles;
+    e->gp_passes = e->gp_pieces = e->gp_tiles = 0;
+    return UVHTTP_WS_GPU_OK;
+}
+
+// kMaxGrid: the product's piece limit and the largest UVHTTP_WS_GRID_PIECE; host only.
+uint64_t uvhttp_ws_gpu_test_max_grid(void) { return kMaxGrid; }
+
+// for_grid_chunks(piece, tiles, ...) itself, host only, no device needed: the (grid, base) pair
+// of each launch into grids[] / bases[] (the first `cap` of them); returns the number of launches.
+uint64_t uvhttp_ws_gpu_test_grid_chunks(uint64_t piece, uint64_t tiles, uint32_t* grids,
+                                        uint64_t* bases, uint64_t cap) {
+    if (!piece) return 0;
+    uint64_t k = 0;
+    return for_grid_chunks(piece, tiles, [&](uint32_t grid, uint64_t base) {
+        if (k < cap) {
+            if (grids) grids[k] = grid;
+            if (bases) bases[k] = base;
+        }
+        ++k;
+    });
 }
 #endif
 
@@ -6329,6 +6370,20 @@ int uvws_set_err(uvhttp_ws_gpu_engine_t* e, int code, const char* what) {
     return set_err(e, code, what, hipSuccess);
 }
 
+uint64_t uvws_grid_piece(const uvhttp_ws_gpu_engine_t* e) { return e->grid_piece; }
+
+void uvws_grid_note(uvhttp_ws_gpu_engine_t* e, uint64_t tiles, uint64_t pieces) {
+#ifdef UVWS_EXPERIMENTS
+    if (pieces) {  // (an empty pass launches nothing and is not counted)
+        e->gp_passes += 1;
+        e->gp_pieces += pieces;
+        e->gp_tiles += tiles;
+    }
+#else
+    (void)e, (void)tiles, (void)pieces;
+#endif
+}
+
 // k_plan launch: frames per lane chosen so the grid stays within ~512 blocks — every block
 // costs a ticket atomic and a look-back round on device-coherent records, so the call's time
 // grows with the block count (C4, 1 048 576 frames: 4096 blocks 148 us, 2048 96, 1024 82,
@@ -6487,7 +6542,7 @@ static int decode_fused(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, B
         // (desc_emit >= 2: no info bytes — the scan and k_desc_emit rebuild them from the records)
         const bool from_rec = e->desc_emit >= 2;
         const int stk = timing_begin(e, s);
-        for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+        engine_grid_chunks(e, f_tiles, [&](uint32_t grid_p, uint64_t tb) {
             if (from_rec)
                 hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveRec>), dim3(grid_p), dim3(256), 0, s, a,
                                    e->ws, tb);
@@ -6512,7 +6567,7 @@ static int decode_fused(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, B
     if (sum_fast) {
         // (a.recs: the info bytes, 1 per frame)
         const int stk = timing_begin(e, s);
-        for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+        engine_grid_chunks(e, f_tiles, [&](uint32_t grid_p, uint64_t tb) {
             hipLaunchKernelGGL((k_unmask_stride<256, 4, false, kLeaveInfo>), dim3(grid_p), dim3(256), 0, s, a,
                                e->ws, tb);
         });
@@ -6524,7 +6579,7 @@ static int decode_fused(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, B
     if (const int rc = own_desc(e, &d_desc, a.n, s)) return rc;
     const int ftk = timing_begin(e, s);
     bool known = true;  // (the shapes set_tile accepts)
-    for_grid_chunks(f_tiles, [&](uint32_t grid_p, uint64_t tb) {
+    engine_grid_chunks(e, f_tiles, [&](uint32_t grid_p, uint64_t tb) {
         known = known && tile_dispatch(fb, fv, [&](auto t) {
             constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
             hipLaunchKernelGGL((k_unmask_stride<B, V>), dim3(grid_p), dim3(B), 0, s, a, e->ws, tb);
@@ -6573,7 +6628,7 @@ static int decode_spec(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, Ba
     const bool desc_c = !no_desc && e->desc_emit && sum_ok(e, b) && a.arena_cap / spec_p >= a.n;
     // (sum_c: a.recs holds the info bytes)
     const int stk = timing_begin(e, s);
-    for_grid_chunks(s_tiles, [&](uint32_t grid_s, uint64_t tb) {
+    engine_grid_chunks(e, s_tiles, [&](uint32_t grid_s, uint64_t tb) {
         if (desc_c)
             hipLaunchKernelGGL((k_unmask_stride<256, 4, true, kLeaveBoth>), dim3(grid_s), dim3(256), 0,
                                s, a, e->ws, tb);
@@ -6647,7 +6702,7 @@ static int decode_planned(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b,
     const uint64_t n_fin = (a.n + blk - 1) / blk;
     if (fold_fin && n_ptiles < n_fin) n_ptiles = n_fin;
     const int tk = timing_begin(e, s);
-    for_grid_chunks(a.n ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
+    engine_grid_chunks(e, a.n ? n_ptiles : 0, [&](uint32_t grid_p, uint64_t tb) {
         (void)tile_dispatch(blk, vpt, [&](auto t) {
             constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
             if (!arena)
@@ -6951,7 +7006,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
         hipLaunchKernelGGL(k_sspec_plan, dim3(nsb), dim3(kBlock), 0, s, sa);
         hipLaunchKernelGGL(k_sspec_tiles, dim3((uint32_t)((sp_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sa);
         tk_spec = timing_begin(e, s);
-        for_grid_chunks(sp_tiles, [&](uint32_t g, uint64_t tb) {
+        engine_grid_chunks(e, sp_tiles, [&](uint32_t g, uint64_t tb) {
             hipLaunchKernelGGL(k_sspec_pass, dim3(g), dim3(kBlock), 0, s, sa, tb);
         });
         timing_end(e, tk_spec, s);
@@ -7032,7 +7087,7 @@ int uvhttp_ws_gpu_decode_reads(uvhttp_ws_gpu_engine_t* e, uint8_t* d_wire, uint6
     const uint64_t tile_bytes = (uint64_t)blk * vpt * 16;
     const uint64_t n_ptiles = (wire_len + tile_bytes - 1) / tile_bytes;
     const int tk = e->time_chain ? -1 : timing_begin(e, s);
-    for_grid_chunks(n_ptiles, [&](uint32_t grid_p, uint64_t tb) {
+    engine_grid_chunks(e, n_ptiles, [&](uint32_t grid_p, uint64_t tb) {
         (void)tile_dispatch(blk, vpt, [&](auto t) {
             constexpr int B = decltype(t)::block, V = decltype(t)::vpt;
             hipLaunchKernelGGL((k_unmask_inplace<B, V>), dim3(grid_p), dim3(B), 0, s, a, d_desc, e->ws, tb);
@@ -7137,10 +7192,10 @@ int uvhttp_ws_gpu_build_frames(uvhttp_ws_gpu_engine_t* e, const uint8_t* d_src, 
         if (wide) hipLaunchKernelGGL((kb_emit_frames<256, 256>), grid, dim3(256), 0, s, b);
         else hipLaunchKernelGGL((kb_emit_frames<256, 64>), grid, dim3(256), 0, s, b);
     }
-    else if (sh == 3) launch_emit<256, 4>(b, n_frames, out_cap, s);
-    else if (sh == 2) launch_emit<128, 2>(b, n_frames, out_cap, s);
-    else if (sh == 1) launch_emit<64, 4>(b, n_frames, out_cap, s);
-    else launch_emit<64, 2>(b, n_frames, out_cap, s);
+    else if (sh == 3) launch_emit<256, 4>(e, b, n_frames, out_cap, s);
+    else if (sh == 2) launch_emit<128, 2>(e, b, n_frames, out_cap, s);
+    else if (sh == 1) launch_emit<64, 4>(e, b, n_frames, out_cap, s);
+    else launch_emit<64, 2>(e, b, n_frames, out_cap, s);
     timing_end(e, tk, s);
     return call.finish();
 }
@@ -7159,7 +7214,7 @@ int uvhttp_ws_gpu_apply_mask(uvhttp_ws_gpu_engine_t* e, uint8_t* d_data, uint64_
     hipStream_t s = (hipStream_t)stream;
     EngineCall call(e, s);
     const int tk = timing_begin(e, s);
-    for_grid_chunks(tiles, [&](uint32_t grid, uint64_t tb) {
+    engine_grid_chunks(e, tiles, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_apply_mask, dim3(grid), dim3(kMaskBlock), 0, s, d_data, len, k, head, tb);
     });
     timing_end(e, tk, s);
