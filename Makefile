@@ -45,6 +45,11 @@ $(BUILD)/ws_replies_gpu.o: uvhttp_amd/csrc/ws_replies_gpu.hip include/uvhttp_ws_
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
+# the echo of data messages after a decode: likewise one object for both
+$(BUILD)/ws_echo_gpu.o: uvhttp_amd/csrc/ws_echo_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
 $(BUILD)/tls_gpu.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h $(DEVICE_GUARD)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -78,12 +83,12 @@ $(BUILD)/ws_batcher_group.o: uvhttp_amd/csrc/ws_batcher_group.cpp include/uvhttp
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -fPIC -std=c++17 -Iinclude -Wall -Wextra -Werror -c -o $@ $<
 
-$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
+$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
         $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
-$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
+$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
             $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -108,13 +113,14 @@ tools/bin/copy_probe: tools/copy_probe.cpp $(BUILD)/ws_host.o
 	@mkdir -p tools/bin
 	g++ -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude -o $@ $^ -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
-asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip uvhttp_amd/csrc/utf8_frames_gpu.hip uvhttp_amd/csrc/ws_replies_gpu.hip
+asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip uvhttp_amd/csrc/utf8_frames_gpu.hip uvhttp_amd/csrc/ws_replies_gpu.hip uvhttp_amd/csrc/ws_echo_gpu.hip
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_gpu.s uvhttp_amd/csrc/ws_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/tls_gpu.s uvhttp_amd/csrc/tls_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/utf8_gpu.s uvhttp_amd/csrc/utf8_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/utf8_frames_gpu.s uvhttp_amd/csrc/utf8_frames_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_replies_gpu.s uvhttp_amd/csrc/ws_replies_gpu.hip
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_echo_gpu.s uvhttp_amd/csrc/ws_echo_gpu.hip
 
 clean:
 	rm -rf $(BUILD) uvhttp_amd/lib

@@ -847,6 +847,158 @@ int uvhttp_ws_control_replies(const uint8_t* wire, uint64_t wire_len,
                               uint64_t out_cap, uint64_t* out_off, uint32_t max_replies,
                               uvhttp_ws_reply_conn_t* conn_result);
 
+/* ---- echo of data messages: the echo server's send built on the device after a decode ---- */
+/* The reference's echo server (examples/05_websocket/websocket_echo_server.c) answers every data
+ * message with the same bytes: on_message -> uvhttp_server_ws_send -> uvhttp_ws_send_text ->
+ * uvhttp_ws_send_frame (src/uvhttp_websocket.c:509-608).  These calls build those frames for a
+ * whole decoded batch where it lies in device memory, in the layout the control replies use, so
+ * records in -> decoded frames -> sealed echoes out needs no host step.  build_frames cannot do
+ * it: its frame count is a host argument and one frame has one contiguous source, while a
+ * fragmented message lies in the wire as several payloads with headers, control frames and
+ * possibly a read boundary between them, and its earlier bytes may have arrived in an earlier
+ * call.
+ *
+ * Frames considered.  Connection s: desc[first_frame, first_frame + n_delivered), read from
+ * d_results[s] on the device; the in-place form takes n_delivered from d_batch_summary (one
+ * connection, first_frame 0, nothing carried in).  Frames at or past max_frames are skipped, as
+ * is every frame of a connection whose result is ERR_CAPACITY, ERR_LAYOUT or ERR_DEVICE, and a
+ * descriptor whose status is not OK.  A connection whose d_enable byte is 0 is skipped as a
+ * whole: no echoes, open_len 0, status OK.
+ *
+ * Message membership is the rule uvhttp_ws_gpu_validate_utf8_streams states: a delivered frame
+ * with opcode 1 or 2 starts a message; a delivered CONTINUATION belongs to the message the
+ * nearest earlier delivered start frame of the connection began, or, when there is none, to the
+ * carried-in message: opcode d_streams[s].pending_opcode, pending_bytes != 0.  FIN ends the
+ * message (a CONTINUATION after it and before the next start frame belongs to nothing).  Control
+ * frames in between contribute nothing.
+ *
+ * Which messages are echoed.  A message whose FIN frame is delivered gets ONE frame:
+ * uvhttp_ws_build_frame(payload = all the message's bytes in order, carried bytes first, opcode =
+ * the message's, mask = !is_server, fin = 1), with a header of 2, 4 or 10 bytes by the total
+ * length; an empty message gets an empty frame.  With UVHTTP_WS_ECHO_SERVER_SEND the opcode is
+ * always TEXT and an empty message gets nothing (uvhttp_server_ws_send, src/uvhttp_server.c:
+ * 1057-1089).  A message whose FIN frame comes after the connection's first delivered CLOSE is
+ * not echoed: process_data has set state = CLOSED (:1069) and send_frame refuses (:513).  Echo
+ * slot j (its index in this call's output) of a client connection takes key d_mask_keys[j];
+ * d_mask_keys (max_echoes entries) may be NULL only when every enabled stream is a server: a
+ * client stream then gets status NO_KEYS.
+ *
+ * Carry.  d_carry_off has n_streams + 1 entries; connection s's carried bytes are
+ * d_carry[d_carry_off[s], d_carry_off[s + 1]).  They are usable only when that length equals
+ * d_streams[s].pending_bytes and the range lies inside carry_len (d_carry or d_carry_off NULL:
+ * nothing is usable).  A connection with pending_bytes != 0 and no usable carry gets status
+ * NO_CARRY.  After its last considered frame a connection's message may still be open; its bytes
+ * so far — its carry, then its delivered fragments — are written back to back per connection
+ * into d_open, connection s at d_open_off[s] (n_streams + 1 entries, the last the total): the
+ * carry's own layout, so call k's (d_open, d_open_off, summary.open_bytes) are call k + 1's
+ * (d_carry, d_carry_off, carry_len) as they lie, and open_opcode is the next pending_opcode.  A
+ * connection that considers no frame passes its carry through.  d_open == NULL: open_len and
+ * d_open_off are still written, no bytes are, and open_cap is not tested.  For an enabled
+ * connection with status OK whose decode did not fail, open_len equals d_results[s].pending_bytes.
+ *
+ * Statuses.  NO_KEYS, else NO_CARRY, else BAD_RANGE: a delivered data frame (opcode 0, 1, 2) of
+ * the connection with a payload range outside [0, wire_len).  A connection with any of them gets
+ * no echoes and open_len 0; for NO_KEYS and NO_CARRY nothing is read for it, and nothing outside
+ * the wire or the carry is ever read.
+ *
+ * Layout.  Echoes lie back to back in d_out, connections in index order and a connection's
+ * echoes in frame order of their FIN frames.  d_out_off[j] is the start of echo j, and every
+ * entry from d_out_off[n_echoes] to d_out_off[max_echoes] equals the total: d_out / d_out_off
+ * with n_frames_total = max_echoes is a valid uvhttp_tls_gpu_seal_frames input as it lies.  For
+ * connection s the call writes first_echo and n_echoes at (char*)d_runs + s * run_stride (d_runs
+ * may be NULL), as the control replies write their runs; first_echo is the number of echoes of
+ * the connections before s.
+ *
+ * Capacity.  If the echoes exceed max_echoes, their bytes out_cap or (with d_open) the open bytes
+ * open_cap, nothing is written to d_out or d_open, every d_out_off and d_open_off entry and
+ * every run is 0, every per-connection result is zero but for status ERR_CAPACITY, and the
+ * summary holds the three totals needed with status ERR_CAPACITY.
+ *
+ * After decode_compact data payloads lie in the message arena: pass the arena (and its size) as
+ * d_wire / wire_len of the in-place form; payload_off of data frames already points there.
+ *
+ * Order on one connection.  The reference interleaves echoes and control replies in frame order;
+ * echo_messages and control_replies give two runs.  A caller who seals both sends a connection's
+ * echo run before its control-reply run, so that a CLOSE echo stays last.
+ *
+ * All pointers are device pointers: d_wire, d_out, d_open and d_carry 16-byte aligned, d_desc,
+ * d_streams, d_results, d_batch_summary, d_out_off, d_carry_off, d_open_off, d_conn and
+ * d_summary 8, the rest 4 (d_enable 1).  EINVAL for NULL (d_enable, d_mask_keys, d_runs, d_carry,
+ * d_carry_off and d_open excepted) or misaligned arguments, run_stride < 8 or not a multiple of
+ * 4 (with d_runs), max_frames or max_echoes > 2^28, n_streams > 2^31.  Asynchronous on `stream`
+ * under the engine's stream rule.  Scratch lives in the engine (28 bytes per descriptor, 120 per
+ * connection, 64 per echo slot, 4 per 64 KiB of out_cap and of open_cap, no epoch tags), grown on
+ * demand: graph-capturable once one uncaptured call of the same or a larger shape (max_frames,
+ * n_streams, max_echoes, out_cap, open_cap) has been made; a captured call that would allocate
+ * fails with ENOMEM. */
+#define UVHTTP_WS_ECHO_SERVER_SEND 0x1u  /* flags: as uvhttp_server_ws_send: every echo is a TEXT
+                                            frame, empty messages get none */
+#define UVHTTP_WS_ECHO_OK 0
+#define UVHTTP_WS_ECHO_ERR_CAPACITY 1    /* the whole call: max_echoes, out_cap or open_cap too small */
+#define UVHTTP_WS_ECHO_BAD_RANGE 2       /* a data payload of the connection lies outside the wire */
+#define UVHTTP_WS_ECHO_NO_KEYS 3         /* a client connection and d_mask_keys == NULL */
+#define UVHTTP_WS_ECHO_NO_CARRY 4        /* pending_bytes != 0 and no usable carried bytes */
+
+typedef struct {            /* 32 B, one per connection, device-written */
+    uint32_t first_echo;    /* index of the connection's first echo in d_out_off */
+    uint32_t n_echoes;
+    uint64_t out_len;       /* bytes of its echo frames */
+    uint64_t open_len;      /* bytes of the message still open after its last considered frame */
+    uint8_t status;         /* UVHTTP_WS_ECHO_* */
+    uint8_t open_opcode;    /* that message's opcode (0 when open_len is 0) */
+    uint8_t reserved[6];
+} uvhttp_ws_echo_conn_t;
+
+typedef struct {            /* 32 B */
+    uint64_t out_bytes;     /* bytes of d_out the call needs */
+    uint64_t open_bytes;    /* bytes of d_open the call needs */
+    uint32_t n_echoes;      /* echoes the call needs */
+    int32_t status;         /* UVHTTP_WS_ECHO_OK or UVHTTP_WS_ECHO_ERR_CAPACITY */
+    uint32_t reserved[2];
+} uvhttp_ws_echo_summary_t;
+
+int uvhttp_ws_gpu_echo_messages_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                        uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                        uint32_t max_frames, const uvhttp_ws_stream_t* d_streams,
+                                        const uvhttp_ws_stream_result_t* d_results,
+                                        uint32_t n_streams, const uint8_t* d_enable,
+                                        const uint32_t* d_mask_keys, uint32_t flags,
+                                        const uint8_t* d_carry, uint64_t carry_len,
+                                        const uint64_t* d_carry_off, uint8_t* d_out,
+                                        uint64_t out_cap, uint64_t* d_out_off, uint32_t max_echoes,
+                                        uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open,
+                                        uint64_t open_cap, uint64_t* d_open_off,
+                                        uvhttp_ws_echo_conn_t* d_conn,
+                                        uvhttp_ws_echo_summary_t* d_summary, void* stream);
+int uvhttp_ws_gpu_echo_messages_inplace(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                        uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                        uint32_t n_frames,
+                                        const uvhttp_ws_batch_summary_t* d_batch_summary,
+                                        int32_t is_server, const uint32_t* d_mask_keys,
+                                        uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                                        uint64_t* d_out_off, uint32_t max_echoes, uint32_t* d_runs,
+                                        uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+                                        uint64_t* d_open_off, uvhttp_ws_echo_conn_t* d_conn,
+                                        uvhttp_ws_echo_summary_t* d_summary, void* stream);
+/* Host twin (plain C, host copies): the same bytes and result for one connection,
+ * desc[first_frame, first_frame + n_delivered), with the carried-in message (pending_opcode,
+ * pending_bytes) and its bytes carry[0, carry_len), usable when carry_len == pending_bytes.
+ * Echo j of the connection takes mask_keys[j] and starts at out_off[j] (max_echoes + 1 entries,
+ * the tail filled as above), first_echo is 0; the open message goes to open[0, open_len) (open
+ * may be NULL: open_len is still reported, open_cap is not tested).  The statement of the rules:
+ * "device == host".  On capacity nothing is written to out or open, out_off is all 0 and the
+ * result holds the needed n_echoes, out_len and open_len with status ERR_CAPACITY.  Returns 0,
+ * or -1 for NULL arguments (desc may be NULL when n_delivered is 0, mask_keys when is_server,
+ * out when out_cap is 0, carry when carry_len is 0). */
+int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
+                            const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                            uint32_t n_delivered, int is_server, int enable,
+                            const uint32_t* mask_keys, uint32_t flags, int pending_opcode,
+                            uint64_t pending_bytes, const uint8_t* carry, uint64_t carry_len,
+                            uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                            uint32_t max_echoes, uint8_t* open, uint64_t open_cap,
+                            uvhttp_ws_echo_conn_t* conn_result);
+
 /* ---- host-memory pipeline (libuv read buffers in, decoded payloads out) ---------------- */
 /* A pipeline owns `depth` slots.  Each slot = a pinned host staging buffer (the caller
  * writes masked frames there, e.g. hands it out from the libuv alloc callback) and a device

@@ -138,6 +138,30 @@ class ReplySummary(C.Structure):
         return {k: getattr(self, k) for k in ("out_bytes", "n_replies", "n_closed_conns", "status")}
 
 
+ECHO_SERVER_SEND = 0x1  # UVHTTP_WS_ECHO_SERVER_SEND
+ECHO_OK, ECHO_ERR_CAPACITY, ECHO_BAD_RANGE, ECHO_NO_KEYS, ECHO_NO_CARRY = range(5)
+
+
+class EchoConn(C.Structure):
+    """uvhttp_ws_echo_conn_t (32 B)."""
+    _fields_ = [("first_echo", C.c_uint32), ("n_echoes", C.c_uint32), ("out_len", C.c_uint64),
+                ("open_len", C.c_uint64), ("status", C.c_uint8), ("open_opcode", C.c_uint8),
+                ("reserved", C.c_uint8 * 6)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("first_echo", "n_echoes", "out_len", "open_len", "status",
+                                              "open_opcode")}
+
+
+class EchoSummary(C.Structure):
+    """uvhttp_ws_echo_summary_t (32 B)."""
+    _fields_ = [("out_bytes", C.c_uint64), ("open_bytes", C.c_uint64), ("n_echoes", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("out_bytes", "open_bytes", "n_echoes", "status")}
+
+
 class Stream(C.Structure):
     """uvhttp_ws_stream_t (64 B)."""
     _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("recv_buffer_size", C.c_uint64),
@@ -374,6 +398,14 @@ def load_library(path: str) -> C.CDLL:
                                                             u64, vp, u32, vp, u32, vp, vp, vp]),
         "uvhttp_ws_control_replies": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, vp,
                                                 u64, vp, u32, C.POINTER(ReplyConn)]),
+        "uvhttp_ws_gpu_echo_messages_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32,
+                                                          vp, u64, vp, vp, u64, vp, u32, vp, u32, vp, u64,
+                                                          vp, vp, vp, vp]),
+        "uvhttp_ws_gpu_echo_messages_inplace": (C.c_int, [vp, vp, u64, vp, u32, vp, i32, vp, u32, vp, u64,
+                                                          vp, u32, vp, u32, vp, u64, vp, vp, vp, vp]),
+        "uvhttp_ws_echo_messages": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, C.c_int,
+                                              u64, vp, u64, vp, u64, vp, u32, vp, u64,
+                                              C.POINTER(EchoConn)]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -582,6 +614,37 @@ def control_replies(wire, desc, first_frame, n_delivered, is_server=1, enable=1,
         raise ValueError("uvhttp_ws_control_replies: bad argument")
     ok = res.status != REPLY_ERR_CAPACITY
     return bytes(out)[: res.out_len if ok else 0], list(off), res.as_dict()
+
+
+def echo_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, mask_keys=None,
+                  flags=0, pending_opcode=0, pending_bytes=0, carry=None, out_cap=None,
+                  max_echoes=None, open_cap=None, want_open=True, wire_len=None):
+    """uvhttp_ws_echo_messages: the host twin of GpuEngine.echo_messages_streams / _inplace for
+    one connection.  `wire` / `desc` as utf8_judge_frames; mask_keys = a sequence of 32-bit keys,
+    one per echo slot (None: no table); carry = the carried-in bytes (None: none).  out_cap /
+    max_echoes / open_cap default to what the connection can need.  -> (out bytes [out_len],
+    out_off list [max_echoes + 1], open bytes [open_len], EchoConn.as_dict())."""
+    wb = _host_buf(wire)
+    db = _host_buf(desc)
+    n = len(wire) if wire_len is None else wire_len
+    carry = b"" if carry is None else bytes(carry)
+    max_echoes = n_delivered if max_echoes is None else max_echoes
+    out_cap = 14 * n_delivered + n + len(carry) if out_cap is None else out_cap
+    open_cap = n + len(carry) if open_cap is None else open_cap
+    out = (C.c_uint8 * max(1, out_cap))()
+    opn = (C.c_uint8 * max(1, open_cap))() if want_open else None
+    off = (C.c_uint64 * (max_echoes + 1))()
+    kb = None if mask_keys is None else (C.c_uint32 * max(1, len(mask_keys)))(*mask_keys)
+    cb = (C.c_uint8 * max(1, len(carry))).from_buffer_copy(carry or b"\0")
+    res = EchoConn()
+    rc = lib().uvhttp_ws_echo_messages(wb, n, db, first_frame, n_delivered, is_server, enable, kb,
+                                       flags, pending_opcode, pending_bytes, cb, len(carry), out,
+                                       out_cap, off, max_echoes, opn, open_cap, C.byref(res))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_echo_messages: bad argument")
+    ok = res.status != ECHO_ERR_CAPACITY
+    return (bytes(out)[: res.out_len if ok else 0], list(off),
+            bytes(opn)[: res.open_len if ok else 0] if want_open else b"", res.as_dict())
 
 
 class WsConnection:
@@ -1007,6 +1070,74 @@ class GpuEngine:
             C.c_void_p(conn.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream(stream)),
             "control_replies_inplace")
         return out, out_off, conn, summary
+
+    def _echo_out(self, n_streams, max_echoes, out_cap, out, out_off, open_off, conn, summary):
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = t.zeros(max(16, out_cap), dtype=t.uint8, device=dev)
+        if out_off is None:
+            out_off = t.zeros(max_echoes + 1, dtype=t.int64, device=dev)
+        if open_off is None:
+            open_off = t.zeros(n_streams + 1, dtype=t.int64, device=dev)
+        if conn is None:
+            conn = t.zeros(max(1, n_streams) * C.sizeof(EchoConn), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(EchoSummary), dtype=t.uint8, device=dev)
+        return out, out_off, open_off, conn, summary
+
+    def echo_messages_streams(self, wire, desc, max_frames, streams_dev, results, n_streams,
+                              max_echoes, out_cap, enable=None, mask_keys=None, flags=0, carry=None,
+                              carry_len=0, carry_off=None, out=None, out_off=None, runs=None,
+                              run_stride=8, open=None, open_cap=0, open_off=None, conn=None,
+                              summary=None, wire_len=None, stream=None):
+        """uvhttp_ws_gpu_echo_messages_streams after decode_streams / decode_reads over the same
+        device tensors: one echo frame per data message whose FIN frame was delivered, gathered
+        from its fragments and from the carried-in bytes (carry / carry_off, device tensors, or
+        None), and the messages still open into `open` / open_off (open=None: sizes only).
+        enable, mask_keys and runs as control_replies_streams.  Returns (out, out_off, open_off,
+        conn, summary) device tensors: the frames, max_echoes + 1 and n_streams + 1 int64
+        offsets, n_streams 32-byte uvhttp_ws_echo_conn_t and the uvhttp_ws_echo_summary_t."""
+        out, out_off, open_off, conn, summary = self._echo_out(n_streams, max_echoes, out_cap, out,
+                                                               out_off, open_off, conn, summary)
+        self._check(self._L.uvhttp_ws_gpu_echo_messages_streams(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), max_frames, C.c_void_p(streams_dev.data_ptr()),
+            C.c_void_p(results.data_ptr()), n_streams, self._ptr(enable), self._ptr(mask_keys), flags,
+            self._ptr(carry), carry_len, self._ptr(carry_off), C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_echoes, self._ptr(runs), run_stride, self._ptr(open),
+            open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
+            C.c_void_p(summary.data_ptr()), self._stream(stream)), "echo_messages_streams")
+        return out, out_off, open_off, conn, summary
+
+    def echo_messages_inplace(self, wire, desc, n_frames, batch_summary, max_echoes, out_cap,
+                              is_server=1, mask_keys=None, flags=0, out=None, out_off=None, runs=None,
+                              run_stride=8, open=None, open_cap=0, open_off=None, conn=None,
+                              summary=None, wire_len=None, stream=None):
+        """uvhttp_ws_gpu_echo_messages_inplace after decode_inplace, or after decode_compact with
+        the arena as `wire`: one connection.  Returns as echo_messages_streams."""
+        out, out_off, open_off, conn, summary = self._echo_out(1, max_echoes, out_cap, out, out_off,
+                                                               open_off, conn, summary)
+        self._check(self._L.uvhttp_ws_gpu_echo_messages_inplace(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), n_frames, C.c_void_p(batch_summary.data_ptr()), is_server,
+            self._ptr(mask_keys), flags, C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_echoes, self._ptr(runs), run_stride, self._ptr(open),
+            open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
+            C.c_void_p(summary.data_ptr()), self._stream(stream)), "echo_messages_inplace")
+        return out, out_off, open_off, conn, summary
+
+    @staticmethod
+    def read_echo_conns(conn, n):
+        """host copy of the first n per-connection echo results -> [dict] (EchoConn.as_dict)"""
+        sz = C.sizeof(EchoConn)
+        raw = bytes(conn[: n * sz].cpu().numpy().tobytes())
+        return [EchoConn.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_echo_summary(summary) -> dict:
+        raw = bytes(summary.cpu().numpy().tobytes())
+        return EchoSummary.from_buffer_copy(raw).as_dict()
 
     @staticmethod
     def read_reply_conns(conn, n):

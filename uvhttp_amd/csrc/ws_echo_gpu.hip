@@ -1,0 +1,980 @@
+// ws_echo_gpu.hip — the echo server's data frames built on the device after a decode
+// (include/uvhttp_ws_amd.h: uvhttp_ws_gpu_echo_messages_streams / _inplace): for every message
+// whose FIN frame was delivered, the one frame on_message -> uvhttp_ws_send_text / _send_binary
+// puts on the wire (src/uvhttp_websocket.c:509-608), gathered from the message's fragments where
+// they lie in the decoded wire and from the bytes carried in from earlier calls; and the bytes of
+// every message still open, laid out as the next call's carry.  Short launches over descriptors
+// and connections, scratch in the engine, no waiting between workgroups, then one byte mover:
+//
+//   k_echo_init     marks[f] = 0 per descriptor; the summary zeroed
+//   k_echo_conns    one lane per connection: its state word (enabled, NO_KEYS, NO_CARRY, carries
+//                   in), its scratch words, a head mark at its first considered descriptor
+//   k_echo_reduce / k_echo_top   the scan of the head marks (as the control replies')
+//   k_echo_classify one lane per descriptor, 32 bytes read: its connection; a word — in range,
+//                   first / last of the range, a delivered data frame, start of a message, FIN;
+//                   first_close[connection] (atomicMin), bad[connection] for a payload outside
+//                   the wire.  The workgroup's data-payload bytes and its last message marker
+//   k_echo_top      both aggregates
+//   k_echo_prefix   one lane per descriptor: dsum[f] = data-payload bytes before f (a message's
+//                   length is a difference of two of them plus its carry), and view[f] = the
+//                   message f belongs to: the nearest earlier start frame, or the head of the
+//                   connection's range when a message was carried in, unless a FIN lies between
+//   k_echo_size     one lane per descriptor: the lane of a FIN frame decides whether its message
+//                   is echoed (not after the first CLOSE, not empty under SERVER_SEND, connection
+//                   not bad) and sizes the frame; the lane of a range's last frame sizes the
+//                   message still open.  The workgroup's echoes and bytes
+//   k_echo_top, k_echo_creduce, k_echo_top   the totals: echoes, bytes, open bytes — the one set
+//                   every writer goes by
+//   k_echo_offsets  one lane per descriptor: slot and offset from the scan; d_out_off[j] and the
+//                   echo's record (where its bytes come from), written by the FIN frame's lane;
+//                   the running totals before a connection's first frame and after its last
+//   k_echo_tail     d_out_off[n_echoes .. max_echoes] = the total (all 0 on capacity)
+//   k_echo_creduce / k_echo_top / k_echo_finish   one lane per connection: first_echo and
+//                   d_open_off as exclusive sums, the 32-byte result, the run, the open message's
+//                   record, the summary
+//   k_echo_emit     the hot path: P bytes read, H + P written.  One workgroup per 64 KiB tile of
+//                   d_out, then of d_open (tile counts from out_cap / open_cap; tiles past the
+//                   totals return).  The record of a tile's first byte is in a map k_echo_offsets
+//                   / k_echo_finish wrote (the lane of a record notes it for every tile that
+//                   starts inside it), so the tile's records are map[tile] .. map[tile + 1].
+//                   Every lane owns aligned 16-byte vectors of the tile, four side by side so
+//                   that their loads overlap: it finds each vector's record inside that window
+//                   (a search over d_out_off / d_open_off, the same number of steps in every
+//                   lane), and stores the whole vector — an unaligned 16-byte source window
+//                   XOR-ed with the rotated key — when it is payload of the record's carry or of
+//                   its only fragment.  Other vectors go the long way: the source frame by a
+//                   search over dsum inside the record's frames, or byte by byte (headers,
+//                   fragment joins, record joins).  A tile that is payload of one record from one
+//                   source skips all of it: one record read, sixteen loads per lane in flight.
+//                   Only the last vector of an output may take byte stores
+//
+// The descriptor order is the output order: records ascend in their destination, and so do a
+// record's frames (dsum), so nothing is sorted.  A table whose connections' ranges overlap gets
+// unspecified bytes, but nothing outside the wire, the carry, the descriptors below max_frames,
+// the n_streams entries, d_out below out_cap, d_open below open_cap and the offset tables is read
+// or written: every source frame is one whose range k_echo_classify checked, and the emit is
+// bounded by the totals the capacity test used.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "uvhttp_ws_amd.h"
+#include "ws_engine_int.h"
+
+namespace {
+
+constexpr int kBlock = 256;  // the scan block: descriptors (or connections) per workgroup
+constexpr int kWaves = kBlock / 64;
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr int kBatch = 4;     // vectors a lane of the emit handles side by side
+constexpr int kBatches = 4;   // ... this many times
+constexpr int kVecPerLane = kBatch * kBatches;
+constexpr uint64_t kTile = (uint64_t)kBlock * 16 * kVecPerLane;  // output bytes per emit workgroup: 64 KiB
+
+// the word per descriptor (elem)
+constexpr uint64_t kIn = 1ull << 0;      // inside its connection's considered range
+constexpr uint64_t kFirst = 1ull << 1;   // the range's first frame
+constexpr uint64_t kLast = 1ull << 2;    // the range's last frame
+constexpr uint64_t kData = 1ull << 3;    // a delivered data frame of an active connection, range checked
+constexpr uint64_t kStart = 1ull << 4;   // ... with opcode 1 or 2
+constexpr uint64_t kFin = 1ull << 5;     // ... with FIN
+constexpr uint64_t kCarryHead = 1ull << 6;  // kFirst of a connection that carries a message in
+constexpr uint64_t kEcho = 1ull << 7;    // the FIN frame of an echoed message (k_echo_size)
+// bits 32-63: the connection
+
+// the word per connection (cstate): bits 0-7 the static status, then
+constexpr uint32_t kCActive = 1u << 8;   // enabled and neither NO_KEYS nor NO_CARRY
+constexpr uint32_t kCCarry = 1u << 9;    // active and pending_bytes != 0 (the carry is usable)
+
+// a message marker: (frame + 1) << 2 | kind; 0 = no marker
+constexpr uint64_t kMsgNone = 0, kMsgStart = 1, kMsgCarried = 2, kMsgCarryOnly = 3;
+__device__ __forceinline__ uint64_t marker(uint64_t f, uint64_t kind) { return ((f + 1) << 2) | kind; }
+
+struct EcRec {  // where one output frame's (or one open message's) bytes come from
+    uint64_t dbase;      // dsum of the first frame that can hold a fragment
+    uint64_t len;        // payload bytes: carry + fragments
+    uint64_t carry_src;  // offset of the carried bytes in d_carry
+    uint64_t carry_len;
+    uint64_t src0;       // one: the single fragment's payload_off
+    uint32_t g, fend;    // the fragments lie in desc[g, fend]
+    uint32_t key;
+    uint8_t hdr, b0, masked, one;  // header bytes (key included; 0 for an open message), first byte;
+                                   // one: desc[g] is the message's only fragment (g == fend)
+    uint64_t pad;
+};
+static_assert(sizeof(EcRec) == 64, "record");
+
+struct EcArgs {
+    const uint8_t* wire;
+    uint64_t wire_len;
+    const uvhttp_ws_frame_desc_t* desc;
+    uint32_t max_frames;
+    uint32_t n_streams;
+    const uvhttp_ws_stream_t* streams;           // null: the in-place form (one connection)
+    const uvhttp_ws_stream_result_t* results;
+    const uvhttp_ws_batch_summary_t* bsum;       // the in-place form's n_delivered
+    int32_t is_server;                           // the in-place form's
+    const uint8_t* enable;                       // or null
+    const uint32_t* keys;                        // or null
+    uint32_t flags;
+    const uint8_t* carry;                        // or null
+    uint64_t carry_len;
+    const uint64_t* carry_off;                   // or null
+    uint8_t* out;
+    uint64_t out_cap;
+    uint64_t* out_off;
+    uint32_t max_echoes;
+    uint32_t* runs;                              // or null
+    uint32_t run_stride;                         // bytes
+    uint8_t* open;                               // or null
+    uint64_t open_cap;
+    uint64_t* open_off;
+    uvhttp_ws_echo_conn_t* conn;
+    uvhttp_ws_echo_summary_t* sum;
+    // engine scratch
+    uint32_t* marks;        // [max_frames] connection + 1 at its first considered descriptor
+    uint64_t* elem;         // [max_frames] the word above
+    uint64_t* dsum;         // [max_frames] data-payload bytes of the descriptors before f
+    uint64_t* view;         // [max_frames] the marker of the message f belongs to
+    uint64_t* agg_mark;     // [blocks] last head mark, then inclusive
+    uint64_t* agg_d;        // [blocks] data-payload bytes, then inclusive
+    uint64_t* agg_post;     // [blocks] last message marker, then inclusive
+    uint64_t* agg_cnt;      // [blocks] echoes, then inclusive
+    uint64_t* agg_bytes;    // [blocks] echo bytes, then inclusive
+    uint64_t* agg_cn;       // [connection blocks] echoes, then inclusive
+    uint64_t* agg_co;       // [connection blocks] open bytes, then inclusive
+    const uint64_t* tot_cnt;    // &agg_cnt[blocks - 1], null when there is no descriptor
+    const uint64_t* tot_bytes;
+    const uint64_t* tot_open;   // &agg_co[connection blocks - 1], null when there is no connection
+    uint32_t* cstate;       // [n_streams] the word above
+    uint32_t* first_close;  // [n_streams] the connection's first delivered CLOSE, kNone if none
+    uint32_t* bad;          // [n_streams] a data payload outside the wire
+    uint32_t* cbeg;         // [n_streams] echoes before the connection's first frame ...
+    uint32_t* cend;         // ... and up to its last
+    uint64_t* bbeg;         // the same in bytes
+    uint64_t* bend;
+    uint64_t* olen;         // [n_streams] bytes of the message still open
+    uint64_t* omark;        // [n_streams] its marker (frame g and kind)
+    uint32_t* ofend;        // [n_streams] the range's last frame
+    EcRec* rec;             // [max_echoes] the echoes' records
+    EcRec* orec;            // [n_streams] the open messages' records
+    uint32_t* tmap;         // [tiles of d_out] the record that holds the tile's first byte
+    uint32_t* omap;         // [tiles of d_open] likewise
+};
+
+struct LastOp {  // the later mark
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return b ? b : a; }
+};
+struct AddOp {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
+};
+
+// inclusive scan over the workgroup's kBlock lanes; *total = all of them.  Every lane calls it.
+template <typename Op>
+__device__ __forceinline__ uint64_t block_scan(uint64_t v, Op op, uint64_t* s_wave, uint64_t* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(v, d);
+        if (lane >= d) v = op(o, v);
+    }
+    __syncthreads();  // s_wave may still be read from the previous use
+    if (lane == 63) s_wave[w] = v;
+    __syncthreads();
+    uint64_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+        if (k < w) pre = op(pre, s_wave[k]);
+        tot = op(tot, s_wave[k]);
+    }
+    *total = tot;
+    return op(pre, v);
+}
+
+__device__ __forceinline__ bool range_ok(uint64_t limit, uint64_t off, uint64_t len) {
+    return len <= limit && off <= limit - len;
+}
+
+// connection s's considered descriptors [ff, ff + nd), inside [0, max_frames)
+struct EcRange {
+    uint32_t ff, nd;
+};
+
+__device__ __forceinline__ EcRange conn_range(const EcArgs& a, uint32_t s) {
+    EcRange r;
+    if (!a.results) {
+        r.ff = 0;
+        r.nd = a.bsum->n_delivered;
+    } else {
+        const uvhttp_ws_stream_result_t& q = a.results[s];
+        r.ff = q.first_frame;
+        r.nd = q.n_delivered;
+        if (q.first_status == UVHTTP_WS_FRAME_ERR_CAPACITY || q.first_status == UVHTTP_WS_FRAME_ERR_LAYOUT ||
+            q.first_status == UVHTTP_WS_FRAME_ERR_DEVICE)
+            r.nd = 0;
+    }
+    if (r.ff >= a.max_frames) r.nd = 0;
+    else if (r.nd > a.max_frames - r.ff) r.nd = a.max_frames - r.ff;
+    return r;
+}
+
+__device__ __forceinline__ bool conn_server(const EcArgs& a, uint32_t s) {
+    return a.streams ? a.streams[s].is_server != 0 : a.is_server != 0;
+}
+__device__ __forceinline__ uint64_t conn_pending(const EcArgs& a, uint32_t s) {
+    return a.streams ? a.streams[s].pending_bytes : 0;
+}
+__device__ __forceinline__ uint32_t conn_pending_opcode(const EcArgs& a, uint32_t s) {
+    return a.streams ? (uint32_t)a.streams[s].pending_opcode & 0x0Fu : 0u;
+}
+
+// the three totals and the capacity test every writer goes by
+struct EcTotals {
+    uint64_t cnt, bytes, open;
+    bool fits;
+};
+__device__ __forceinline__ EcTotals totals(const EcArgs& a) {
+    EcTotals t;
+    t.cnt = a.tot_cnt ? *a.tot_cnt : 0;
+    t.bytes = a.tot_bytes ? *a.tot_bytes : 0;
+    t.open = a.tot_open ? *a.tot_open : 0;
+    t.fits = t.cnt <= a.max_echoes && t.bytes <= a.out_cap && (!a.open || t.open <= a.open_cap);
+    return t;
+}
+
+__device__ __forceinline__ uint32_t header_bytes(uint64_t len, bool masked) {
+    return (len <= 125 ? 2u : len <= 65535 ? 4u : 10u) + (masked ? 4u : 0u);
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_init(EcArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) {
+        uvhttp_ws_echo_summary_t z = {};
+        *a.sum = z;
+        a.open_off[0] = 0;
+    }
+    if (i < a.max_frames) a.marks[i] = 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_conns(EcArgs a) {
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= a.n_streams) return;
+    a.first_close[s] = kNone;
+    a.bad[s] = 0;
+    a.cbeg[s] = 0;
+    a.cend[s] = 0;
+    a.bbeg[s] = 0;
+    a.bend[s] = 0;
+    a.ofend[s] = 0;
+    uint32_t st = 0;
+    const uint64_t pend = conn_pending(a, (uint32_t)s);
+    if (!a.enable || a.enable[s] != 0) {
+        if (!conn_server(a, (uint32_t)s) && !a.keys) {
+            st = UVHTTP_WS_ECHO_NO_KEYS;
+        } else if (pend != 0) {
+            bool usable = false;
+            if (a.carry && a.carry_off) {
+                const uint64_t lo = a.carry_off[s], hi = a.carry_off[s + 1];
+                usable = hi >= lo && hi <= a.carry_len && hi - lo == pend;
+            }
+            st = usable ? (kCActive | kCCarry) : (uint32_t)UVHTTP_WS_ECHO_NO_CARRY;
+        } else {
+            st = kCActive;
+        }
+    }
+    a.cstate[s] = st;
+    const EcRange r = conn_range(a, (uint32_t)s);
+    if (r.nd) a.marks[r.ff] = (uint32_t)s + 1;
+    // a connection that considers no frame passes its carry through
+    const bool through = !r.nd && (st & kCCarry);
+    a.olen[s] = through ? pend : 0;
+    a.omark[s] = through ? marker(0, kMsgCarryOnly) : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_reduce(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t m = f < a.max_frames ? a.marks[f] : 0;
+    uint64_t tot;
+    (void)block_scan(m, LastOp(), s_wave, &tot);
+    if (threadIdx.x == 0) a.agg_mark[blockIdx.x] = tot;
+}
+
+// one workgroup: agg[0, n) -> inclusive prefixes.  Every lane folds its own run of entries, the
+// runs' totals are scanned once, and the lane writes its run back with the prefix in front.
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void k_echo_top(uint64_t* agg, uint32_t n) {
+    __shared__ uint64_t s_wave[kWaves];
+    __shared__ uint64_t s_last[kWaves];
+    const uint32_t per = (n + kBlock - 1) / kBlock;
+    const uint64_t lo = (uint64_t)threadIdx.x * per;
+    const uint64_t hi = lo + per < n ? lo + per : n;
+    uint64_t run = 0;
+    for (uint64_t i = lo; i < hi; ++i) run = Op()(run, agg[i]);
+    uint64_t tot;
+    const uint64_t inc = block_scan(run, Op(), s_wave, &tot);
+    const uint64_t left = __shfl_up(inc, 1);  // the runs before this lane's
+    if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint64_t acc = (threadIdx.x & 63) ? left : (threadIdx.x ? s_last[(threadIdx.x >> 6) - 1] : 0);
+    for (uint64_t i = lo; i < hi; ++i) {
+        acc = Op()(acc, agg[i]);
+        agg[i] = acc;
+    }
+}
+
+// what frame f posts for the frames after it: a FIN data frame ends the message, a start frame
+// begins one, the head of a range begins the carried-in one (or none)
+__device__ __forceinline__ uint64_t posted_of(uint64_t e, uint64_t f) {
+    if (!(e & kIn)) return 0;
+    if ((e & kData) && (e & kFin)) return marker(f, kMsgNone);
+    if (e & kStart) return marker(f, kMsgStart);
+    if (e & kFirst) return marker(f, (e & kCarryHead) ? kMsgCarried : kMsgNone);
+    return 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_classify(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = f < a.max_frames;
+    const uint64_t m = live ? a.marks[f] : 0;
+    const uint64_t pre = blockIdx.x ? a.agg_mark[blockIdx.x - 1] : 0;
+    uint64_t tot;
+    const uint64_t head = LastOp()(pre, block_scan(m, LastOp(), s_wave, &tot));
+    uint64_t e = 0, plen = 0;
+    if (live && head != 0 && head - 1 < a.n_streams) {
+        const uint32_t conn = (uint32_t)(head - 1);
+        const EcRange r = conn_range(a, conn);
+        if (f >= r.ff && f - r.ff < r.nd) {
+            const uint32_t cs = a.cstate[conn];
+            e = kIn | ((uint64_t)conn << 32) | (f == r.ff ? kFirst : 0) | (f - r.ff == r.nd - 1 ? kLast : 0);
+            if (f == r.ff && (cs & kCCarry)) e |= kCarryHead;
+            const uvhttp_ws_frame_desc_t& d = a.desc[f];
+            const uint32_t op = d.opcode;
+            if (d.status == UVHTTP_WS_FRAME_OK) {
+                if (op == UVHTTP_WS_OPCODE_CLOSE) atomicMin(&a.first_close[conn], (uint32_t)f);
+                if ((cs & kCActive) && op <= UVHTTP_WS_OPCODE_BINARY) {
+                    const uint64_t len = d.payload_len;
+                    if (len != 0 && !range_ok(a.wire_len, d.payload_off, len)) {
+                        a.bad[conn] = 1;
+                    } else {
+                        plen = len;
+                        e |= kData | (op != UVHTTP_WS_OPCODE_CONTINUATION ? kStart : 0) |
+                             ((d.flags & UVHTTP_WS_FLAG_FIN) ? kFin : 0);
+                    }
+                }
+            }
+        }
+    }
+    if (live) a.elem[f] = e;
+    uint64_t tot_d, tot_p;
+    (void)block_scan(plen, AddOp(), s_wave, &tot_d);
+    (void)block_scan(posted_of(e, f), LastOp(), s_wave, &tot_p);
+    if (threadIdx.x == 0) {
+        a.agg_d[blockIdx.x] = tot_d;
+        a.agg_post[blockIdx.x] = tot_p;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_prefix(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    __shared__ uint64_t s_inc[kBlock];
+    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = f < a.max_frames;
+    const uint64_t e = live ? a.elem[f] : 0;
+    const uint64_t plen = (e & kData) ? a.desc[f].payload_len : 0;
+    uint64_t tot;
+    const uint64_t inc_d = (blockIdx.x ? a.agg_d[blockIdx.x - 1] : 0) + block_scan(plen, AddOp(), s_wave, &tot);
+    s_inc[threadIdx.x] = block_scan(posted_of(e, f), LastOp(), s_wave, &tot);
+    __syncthreads();
+    const uint64_t before = LastOp()(blockIdx.x ? a.agg_post[blockIdx.x - 1] : 0, threadIdx.x ? s_inc[threadIdx.x - 1] : 0);
+    if (!live) return;
+    a.dsum[f] = inc_d - plen;
+    uint64_t v = 0;
+    if (e & kIn) {
+        if (e & kStart) v = marker(f, kMsgStart);
+        else if (e & kFirst) v = marker(f, (e & kCarryHead) ? kMsgCarried : kMsgNone);
+        else v = before;
+    }
+    a.view[f] = v;
+}
+
+// the bytes so far, frame f included, of the message `v` names (kind Start or Carried)
+__device__ __forceinline__ uint64_t message_len(const EcArgs& a, uint64_t v, uint64_t f, uint64_t plen, uint32_t conn) {
+    const uint64_t g = (v >> 2) - 1;
+    return a.dsum[f] + plen - a.dsum[g] + ((v & 3) == kMsgCarried ? conn_pending(a, conn) : 0);
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_size(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint64_t e = f < a.max_frames ? a.elem[f] : 0;
+    uint64_t bytes = 0;
+    if (e & kIn) {
+        const uint32_t conn = (uint32_t)(e >> 32);
+        const uint64_t v = a.view[f];
+        const uint64_t plen = (e & kData) ? a.desc[f].payload_len : 0;
+        const bool in_msg = (v & 3) != kMsgNone && a.bad[conn] == 0;
+        if ((e & kData) && (e & kFin) && in_msg) {
+            const uint64_t len = message_len(a, v, f, plen, conn);
+            if ((uint32_t)f < a.first_close[conn] && !((a.flags & UVHTTP_WS_ECHO_SERVER_SEND) && len == 0)) {
+                e |= kEcho;
+                a.elem[f] = e;
+                bytes = header_bytes(len, !conn_server(a, conn)) + len;
+            }
+        }
+        if ((e & kLast) && in_msg && !((e & kData) && (e & kFin))) {
+            const uint64_t len = message_len(a, v, f, plen, conn);
+            if (len != 0) {
+                a.olen[conn] = len;
+                a.omark[conn] = v;
+                a.ofend[conn] = (uint32_t)f;
+            }
+        }
+    }
+    uint64_t tot_c, tot_b;
+    (void)block_scan((e & kEcho) ? 1 : 0, AddOp(), s_wave, &tot_c);
+    (void)block_scan(bytes, AddOp(), s_wave, &tot_b);
+    if (threadIdx.x == 0) {
+        a.agg_cnt[blockIdx.x] = tot_c;
+        a.agg_bytes[blockIdx.x] = tot_b;
+    }
+}
+
+// record j lies at [o, o + n) of its output: it is the record of every tile that starts inside
+__device__ __forceinline__ void map_tiles(uint32_t* map, uint32_t j, uint64_t o, uint64_t n) {
+    for (uint64_t t = (o + kTile - 1) / kTile; t * kTile < o + n; ++t) map[t] = j;
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_offsets(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t e = f < a.max_frames ? a.elem[f] : 0;
+    const bool echo = (e & kEcho) != 0;
+    const uint32_t conn = (uint32_t)(e >> 32);
+    uint64_t v = 0, len = 0, mine = 0;
+    bool masked = false;
+    if (echo) {
+        v = a.view[f];
+        len = message_len(a, v, f, a.desc[f].payload_len, conn);
+        masked = !conn_server(a, conn);
+        mine = header_bytes(len, masked) + len;
+    }
+    uint64_t tot;
+    const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + block_scan(echo ? 1 : 0, AddOp(), s_wave, &tot);
+    const uint64_t bytes = (blockIdx.x ? a.agg_bytes[blockIdx.x - 1] : 0) + block_scan(mine, AddOp(), s_wave, &tot);
+    if (e & kIn) {
+        if (e & kFirst) {
+            a.cbeg[conn] = (uint32_t)(cnt - (echo ? 1 : 0));
+            a.bbeg[conn] = bytes - mine;
+        }
+        if (e & kLast) {
+            a.cend[conn] = (uint32_t)cnt;
+            a.bend[conn] = bytes;
+        }
+    }
+    if (!echo || !totals(a).fits) return;
+    const uint64_t j = cnt - 1, g = (v >> 2) - 1;
+    const bool carried = (v & 3) == kMsgCarried;
+    a.out_off[j] = bytes - mine;
+    EcRec r;
+    r.dbase = a.dsum[g];
+    r.len = len;
+    r.carry_src = carried ? a.carry_off[conn] : 0;
+    r.carry_len = carried ? conn_pending(a, conn) : 0;
+    r.g = (uint32_t)g;
+    r.fend = (uint32_t)f;
+    r.key = masked ? a.keys[j] : 0u;
+    r.hdr = (uint8_t)header_bytes(len, masked);
+    const uint32_t op = (a.flags & UVHTTP_WS_ECHO_SERVER_SEND) ? (uint32_t)UVHTTP_WS_OPCODE_TEXT
+                        : carried ? conn_pending_opcode(a, conn) : (uint32_t)a.desc[g].opcode;
+    r.b0 = (uint8_t)(0x80u | (op & 0x0Fu));
+    r.masked = masked ? 1 : 0;
+    r.one = g == f ? 1 : 0;
+    r.src0 = a.desc[f].payload_off;
+    r.pad = 0;
+    a.rec[j] = r;
+    map_tiles(a.tmap, (uint32_t)j, bytes - mine, mine);
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_tail(EcArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i > a.max_echoes) return;
+    const EcTotals t = totals(a);
+    if (!t.fits) a.out_off[i] = 0;
+    else if (i >= t.cnt) a.out_off[i] = t.bytes;
+}
+
+// which = 0: the connections' echoes (after k_echo_offsets), 1: their open bytes
+__global__ __launch_bounds__(kBlock) void k_echo_creduce(EcArgs a, int which) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint64_t n = 0;
+    if (s < a.n_streams) n = which ? a.olen[s] : (uint64_t)(a.cend[s] - a.cbeg[s]);
+    uint64_t tot;
+    (void)block_scan(n, AddOp(), s_wave, &tot);
+    if (threadIdx.x == 0) (which ? a.agg_co : a.agg_cn)[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_finish(EcArgs a) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = s < a.n_streams;
+    const uint32_t n = live ? a.cend[s] - a.cbeg[s] : 0;
+    const uint64_t ol = live ? a.olen[s] : 0;
+    uint64_t tot;
+    const uint64_t inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
+    const uint64_t inc_o = (blockIdx.x ? a.agg_co[blockIdx.x - 1] : 0) + block_scan(ol, AddOp(), s_wave, &tot);
+    const EcTotals t = totals(a);
+    if (live) {
+        uvhttp_ws_echo_conn_t r = {};
+        if (!t.fits) {
+            r.status = UVHTTP_WS_ECHO_ERR_CAPACITY;
+            a.open_off[s] = 0;
+            if (s == a.n_streams - 1) a.open_off[s + 1] = 0;
+        } else {
+            const uint32_t cs = a.cstate[s];
+            const uint64_t om = a.omark[s];
+            const uint32_t kind = (uint32_t)(om & 3);
+            r.first_echo = (uint32_t)(inc_n - n);
+            r.n_echoes = n;
+            r.out_len = a.bend[s] - a.bbeg[s];
+            r.open_len = ol;
+            r.status = (uint8_t)(cs & 0xFFu);
+            if (r.status == UVHTTP_WS_ECHO_OK && a.bad[s]) r.status = UVHTTP_WS_ECHO_BAD_RANGE;
+            if (ol != 0)
+                r.open_opcode = (uint8_t)(kind == kMsgStart ? (uint32_t)a.desc[(om >> 2) - 1].opcode & 0x0Fu
+                                                             : conn_pending_opcode(a, (uint32_t)s));
+            a.open_off[s] = inc_o - ol;
+            if (s == a.n_streams - 1) a.open_off[s + 1] = inc_o;
+            EcRec o = {};
+            if (ol != 0) {
+                const bool frames = kind != kMsgCarryOnly;
+                const bool carried = kind != kMsgStart;
+                o.len = ol;
+                o.carry_src = carried ? a.carry_off[s] : 0;
+                o.carry_len = carried ? conn_pending(a, (uint32_t)s) : 0;
+                o.g = frames ? (uint32_t)((om >> 2) - 1) : 1u;  // (1, 0): no frames
+                o.fend = frames ? a.ofend[s] : 0u;
+                o.dbase = frames ? a.dsum[o.g] : 0;
+            }
+            a.orec[s] = o;
+            if (a.open) map_tiles(a.omap, (uint32_t)s, inc_o - ol, ol);
+        }
+        a.conn[s] = r;
+        if (a.runs) {
+            uint32_t* run = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.runs) + s * a.run_stride);
+            run[0] = r.first_echo;
+            run[1] = r.n_echoes;
+        }
+    }
+    if (s == 0) {
+        a.sum->out_bytes = t.bytes;
+        a.sum->open_bytes = t.open;
+        a.sum->n_echoes = (uint32_t)t.cnt;
+        a.sum->status = t.fits ? UVHTTP_WS_ECHO_OK : UVHTTP_WS_ECHO_ERR_CAPACITY;
+    }
+}
+
+// ---- the emit ------------------------------------------------------------------------------------
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t rotr32(uint32_t x, uint32_t s) { return s ? (x >> s) | (x << (32u - s)) : x; }
+
+// 16 bytes at any alignment; the caller has checked that they lie inside the buffer
+__device__ __forceinline__ u32x4 load16_any(const uint8_t* p) {
+    u32x4 r;
+    __builtin_memcpy(&r, p, 16);
+    return r;
+}
+
+// byte i of the record's header image (uvhttp_ws_build_frame: flags + opcode, mask bit + length
+// code, the extended length big-endian, the key)
+__device__ __forceinline__ uint32_t header_byte(const EcRec& r, uint32_t i) {
+    const uint32_t base = r.hdr - (r.masked ? 4u : 0u);
+    if (i == 0) return r.b0;
+    if (i == 1) return (r.masked ? 0x80u : 0u) | (base == 2 ? (uint32_t)r.len : base == 4 ? 126u : 127u);
+    if (i < base) return (uint32_t)(r.len >> (8 * (base - 1 - i))) & 0xFFu;
+    return (r.key >> (8 * (i - base))) & 0xFFu;
+}
+
+// the last index in [lo, hi] whose entry is <= x (entries ascend; the caller knows t[lo] <= x)
+__device__ __forceinline__ uint64_t last_le(const uint64_t* t, uint64_t lo, uint64_t hi, uint64_t x) {
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (t[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the unmasked payload byte at message offset m of record r (0 where a broken table leaves none)
+__device__ __forceinline__ uint32_t payload_byte(const EcArgs& a, const EcRec& r, uint64_t m) {
+    if (m < r.carry_len) return a.carry[r.carry_src + m];
+    if (r.g > r.fend) return 0;
+    const uint64_t q = r.dbase + (m - r.carry_len);
+    const uint64_t i = last_le(a.dsum, r.g, r.fend, q);
+    const uint64_t within = q - a.dsum[i];
+    if (!(a.elem[i] & kData)) return 0;
+    const uvhttp_ws_frame_desc_t& d = a.desc[i];
+    return within < d.payload_len ? a.wire[d.payload_off + within] : 0u;
+}
+
+// the output's destination, offset table and records, and its end inside this tile
+struct EcDst {
+    uint8_t* dst;
+    const uint64_t* offs;
+    const EcRec* recs;
+    uint64_t n_rec, hi;
+};
+
+// one vector the long way: its source frame by a search over dsum when it is payload of one
+// fragment, else byte by byte — header bytes, a join of two sources or of two records, or the
+// output's last bytes
+__device__ __forceinline__ void emit_vector(const EcArgs& a, const EcDst& o, uint64_t x, uint64_t ri) {
+    EcRec r = o.recs[ri];
+    uint64_t r_off = o.offs[ri];
+    const uint64_t rel = x - r_off;
+    if (rel >= r.hdr && rel + 16 <= r.hdr + r.len) {  // the whole vector is payload of one record
+        const uint64_t m = rel - r.hdr;
+        const uint8_t* src = nullptr;
+        if (m + 16 <= r.carry_len) {
+            src = a.carry + r.carry_src + m;
+        } else if (m >= r.carry_len && r.g <= r.fend) {
+            const uint64_t q = r.dbase + (m - r.carry_len);
+            const uint64_t i = last_le(a.dsum, r.g, r.fend, q);
+            const uint64_t within = q - a.dsum[i];
+            if (a.elem[i] & kData) {
+                const uvhttp_ws_frame_desc_t& d = a.desc[i];
+                if (within + 16 <= d.payload_len) src = a.wire + d.payload_off + within;
+            }
+        }
+        if (src) {  // ... and of one source
+            u32x4 w = load16_any(src);
+            if (r.masked) {
+                const uint32_t rk = rotr32(r.key, 8u * (uint32_t)(m & 3u));
+                w ^= u32x4{rk, rk, rk, rk};
+            }
+            *reinterpret_cast<u32x4*>(o.dst + x) = w;
+            return;
+        }
+    }
+    const uint32_t nb = o.hi - x < 16 ? (uint32_t)(o.hi - x) : 16u;
+    uint32_t w[4] = {0, 0, 0, 0};
+    for (uint32_t b = 0; b < nb; ++b) {
+        const uint64_t p = x + b;
+        while (ri + 1 < o.n_rec && o.offs[ri + 1] <= p) {
+            ++ri;
+            r = o.recs[ri];
+            r_off = o.offs[ri];
+        }
+        const uint64_t q = p - r_off;
+        uint32_t v;
+        if (q < r.hdr) {
+            v = header_byte(r, (uint32_t)q);
+        } else {
+            const uint64_t m = q - r.hdr;
+            v = m < r.len ? payload_byte(a, r, m) : 0u;
+            if (r.masked) v ^= (r.key >> (8 * (uint32_t)(m & 3u))) & 0xFFu;
+        }
+        w[b >> 2] |= (v & 0xFFu) << (8 * (b & 3));
+    }
+    if (nb == 16) {
+        *reinterpret_cast<u32x4*>(o.dst + x) = u32x4{w[0], w[1], w[2], w[3]};
+    } else {
+        for (uint32_t b = 0; b < nb; ++b) o.dst[x + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_echo_emit(EcArgs a, uint64_t tile_base, uint64_t tiles_out) {
+    const EcTotals t = totals(a);
+    if (!t.fits) return;
+    uint64_t tile = tile_base + blockIdx.x;
+    const bool to_open = tile >= tiles_out;
+    if (to_open) tile -= tiles_out;
+    const uint64_t total = to_open ? t.open : t.bytes;
+    const uint64_t lo = tile * kTile;
+    if (lo >= total) return;
+    EcDst o;
+    o.hi = lo + kTile < total ? lo + kTile : total;
+    o.dst = to_open ? a.open : a.out;
+    o.offs = to_open ? a.open_off : a.out_off;
+    o.recs = to_open ? a.orec : a.rec;
+    o.n_rec = to_open ? a.n_streams : t.cnt;  // >= 1: total != 0
+    // the records of the tile's first byte and of the next tile's (k_echo_offsets / _finish wrote
+    // them down): every vector's record lies between
+    const uint32_t* map = to_open ? a.omap : a.tmap;
+    uint64_t r_lo = map[tile];
+    uint64_t r_hi = lo + kTile < total ? map[tile + 1] : o.n_rec - 1;
+    if (r_hi > o.n_rec - 1) r_hi = o.n_rec - 1;  // (a table whose ranges overlap: stay inside)
+    if (r_lo > r_hi) r_lo = r_hi;
+
+    // a whole tile that is payload of one record from one source (large messages): one record
+    // read for the workgroup, then every lane's kVecPerLane loads in flight before its stores
+    if (r_lo == r_hi && o.hi - lo == kTile) {
+        const EcRec r = o.recs[r_lo];
+        const uint64_t r_off = o.offs[r_lo];
+        if (lo >= r_off + r.hdr && o.hi <= r_off + r.hdr + r.len) {
+            const uint64_t m = lo - r_off - r.hdr;
+            const uint8_t* base = nullptr;
+            if (m + kTile <= r.carry_len) base = a.carry + r.carry_src + m;
+            else if (m >= r.carry_len && r.one) base = a.wire + r.src0 + (m - r.carry_len);
+            if (base) {
+                const uint32_t rk = r.masked ? rotr32(r.key, 8u * (uint32_t)(m & 3u)) : 0u;  // every vector's: 16 | its offset
+                u32x4 w[kVecPerLane];
+#pragma unroll
+                for (int k = 0; k < kVecPerLane; ++k) w[k] = load16_any(base + ((uint64_t)k * kBlock + threadIdx.x) * 16);
+#pragma unroll
+                for (int k = 0; k < kVecPerLane; ++k)
+                    *reinterpret_cast<u32x4*>(o.dst + lo + ((uint64_t)k * kBlock + threadIdx.x) * 16) = w[k] ^ u32x4{rk, rk, rk, rk};
+                return;
+            }
+        }
+    }
+
+    // else kBatch vectors side by side, so that their loads overlap: the record of each (the same
+    // number of search steps in every lane), the records, the sources
+#pragma unroll 1
+    for (int b = 0; b < kBatches; ++b) {
+    const uint64_t lo_b = lo + (uint64_t)b * kBatch * kBlock * 16;
+    if (lo_b >= o.hi) break;
+    uint64_t x[kBatch], rl[kBatch], rh[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {
+        x[k] = lo_b + ((uint64_t)k * kBlock + threadIdx.x) * 16;
+        rl[k] = r_lo;
+        rh[k] = x[k] < o.hi ? r_hi : r_lo;
+    }
+    for (uint64_t span = r_hi - r_lo; span; span >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kBatch; ++k) {
+            if (rl[k] < rh[k]) {
+                const uint64_t mid = rl[k] + (rh[k] - rl[k] + 1) / 2;
+                if (o.offs[mid] <= x[k]) rl[k] = mid;
+                else rh[k] = mid - 1;
+            }
+        }
+    }
+    const uint8_t* src[kBatch];
+    uint32_t rk[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {
+        src[k] = nullptr;
+        rk[k] = 0;
+        if (x[k] >= o.hi) continue;
+        const EcRec& r = o.recs[rl[k]];
+        const uint64_t rel = x[k] - o.offs[rl[k]];
+        const uint64_t hdr = r.hdr, len = r.len, cl = r.carry_len;
+        if (rel >= hdr && rel + 16 <= hdr + len) {  // payload of one record ...
+            const uint64_t m = rel - hdr;
+            if (m + 16 <= cl) src[k] = a.carry + r.carry_src + m;  // ... from its carry
+            else if (m >= cl && r.one) src[k] = a.wire + r.src0 + (m - cl);  // ... from its only fragment
+            if (r.masked) rk[k] = rotr32(r.key, 8u * (uint32_t)(m & 3u));
+        }
+    }
+    u32x4 w[kBatch];
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k)
+        if (src[k]) w[k] = load16_any(src[k]);
+    uint32_t slow = 0;  // the vectors left for the long way
+#pragma unroll
+    for (int k = 0; k < kBatch; ++k) {
+        if (src[k]) *reinterpret_cast<u32x4*>(o.dst + x[k]) = w[k] ^ u32x4{rk[k], rk[k], rk[k], rk[k]};
+        else if (x[k] < o.hi) slow |= 1u << k;
+    }
+#pragma unroll 1
+    for (int k = 0; k < kBatch; ++k) {
+        if (!(slow >> k & 1u)) continue;
+        static_assert(kBatch == 4, "the selects below");
+        const uint64_t ri = k == 0 ? rl[0] : k == 1 ? rl[1] : k == 2 ? rl[2] : rl[3];
+        emit_vector(a, o, lo_b + ((uint64_t)k * kBlock + threadIdx.x) * 16, ri);
+    }
+    }
+}
+
+size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+
+int ec_run(uvhttp_ws_gpu_engine_t* e, EcArgs a, void* stream, const char* what) {
+    static_assert(sizeof(uvhttp_ws_echo_conn_t) == 32 && sizeof(uvhttp_ws_echo_summary_t) == 32, "ABI");
+    const uint64_t F = a.max_frames, S = a.n_streams, E = a.max_echoes;
+    const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
+    const uint32_t grid_s = (uint32_t)((S + kBlock - 1) / kBlock);
+    const uint64_t nb = blocks ? blocks : 1, ns = grid_s ? grid_s : 1;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes);
+        return at;
+    };
+    const size_t o_elem = take(F * 8), o_dsum = take(F * 8), o_view = take(F * 8);
+    const size_t o_amark = take(nb * 8), o_ad = take(nb * 8), o_apost = take(nb * 8);
+    const size_t o_acnt = take(nb * 8), o_abytes = take(nb * 8), o_acn = take(ns * 8), o_aco = take(ns * 8);
+    const size_t o_bbeg = take(S * 8), o_bend = take(S * 8), o_olen = take(S * 8), o_omark = take(S * 8);
+    const size_t o_rec = take(E * sizeof(EcRec)), o_orec = take(S * sizeof(EcRec));
+    const size_t o_marks = take(F * 4);
+    const uint64_t tiles_out = (a.out_cap + kTile - 1) / kTile;
+    const uint64_t tiles_open = a.open ? (a.open_cap + kTile - 1) / kTile : 0;
+    const size_t o_tmap = take((tiles_out + 1) * 4), o_omap = take((tiles_open + 1) * 4);
+    const size_t o_cstate = take(S * 4), o_close = take(S * 4), o_bad = take(S * 4);
+    const size_t o_cbeg = take(S * 4), o_cend = take(S * 4), o_ofend = take(S * 4);
+
+    hipStream_t s = (hipStream_t)stream;
+    const int prev = uvws_call_enter(e, s);
+    char* mem = static_cast<char*>(uvws_echo_scratch(e, off ? off : 256, s));
+    if (!mem) {
+        (void)uvws_call_leave(e, prev, what);
+        return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "echo_messages scratch (a captured call must not grow it)");
+    }
+    a.elem = reinterpret_cast<uint64_t*>(mem + o_elem);
+    a.dsum = reinterpret_cast<uint64_t*>(mem + o_dsum);
+    a.view = reinterpret_cast<uint64_t*>(mem + o_view);
+    a.agg_mark = reinterpret_cast<uint64_t*>(mem + o_amark);
+    a.agg_d = reinterpret_cast<uint64_t*>(mem + o_ad);
+    a.agg_post = reinterpret_cast<uint64_t*>(mem + o_apost);
+    a.agg_cnt = reinterpret_cast<uint64_t*>(mem + o_acnt);
+    a.agg_bytes = reinterpret_cast<uint64_t*>(mem + o_abytes);
+    a.agg_cn = reinterpret_cast<uint64_t*>(mem + o_acn);
+    a.agg_co = reinterpret_cast<uint64_t*>(mem + o_aco);
+    a.bbeg = reinterpret_cast<uint64_t*>(mem + o_bbeg);
+    a.bend = reinterpret_cast<uint64_t*>(mem + o_bend);
+    a.olen = reinterpret_cast<uint64_t*>(mem + o_olen);
+    a.omark = reinterpret_cast<uint64_t*>(mem + o_omark);
+    a.rec = reinterpret_cast<EcRec*>(mem + o_rec);
+    a.orec = reinterpret_cast<EcRec*>(mem + o_orec);
+    a.marks = reinterpret_cast<uint32_t*>(mem + o_marks);
+    a.tmap = reinterpret_cast<uint32_t*>(mem + o_tmap);
+    a.omap = reinterpret_cast<uint32_t*>(mem + o_omap);
+    a.cstate = reinterpret_cast<uint32_t*>(mem + o_cstate);
+    a.first_close = reinterpret_cast<uint32_t*>(mem + o_close);
+    a.bad = reinterpret_cast<uint32_t*>(mem + o_bad);
+    a.cbeg = reinterpret_cast<uint32_t*>(mem + o_cbeg);
+    a.cend = reinterpret_cast<uint32_t*>(mem + o_cend);
+    a.ofend = reinterpret_cast<uint32_t*>(mem + o_ofend);
+    const bool frames = blocks && grid_s;  // else no echo: the totals are 0
+    a.tot_cnt = frames ? a.agg_cnt + (blocks - 1) : nullptr;
+    a.tot_bytes = frames ? a.agg_bytes + (blocks - 1) : nullptr;
+    a.tot_open = grid_s ? a.agg_co + (grid_s - 1) : nullptr;
+
+    hipLaunchKernelGGL(k_echo_init, dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
+    if (grid_s) hipLaunchKernelGGL(k_echo_conns, dim3(grid_s), dim3(kBlock), 0, s, a);
+    if (frames) {
+        hipLaunchKernelGGL(k_echo_reduce, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, blocks);
+        hipLaunchKernelGGL(k_echo_classify, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_d, blocks);
+        hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_post, blocks);
+        hipLaunchKernelGGL(k_echo_prefix, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(k_echo_size, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cnt, blocks);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_bytes, blocks);
+    }
+    if (grid_s) {
+        hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, a, 1);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_co, grid_s);
+    }
+    if (frames) hipLaunchKernelGGL(k_echo_offsets, dim3(blocks), dim3(kBlock), 0, s, a);
+    const uint32_t grid_t = (uint32_t)((E + 1 + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_echo_tail, dim3(grid_t), dim3(kBlock), 0, s, a);
+    if (grid_s) {
+        hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, a, 0);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cn, grid_s);
+        hipLaunchKernelGGL(k_echo_finish, dim3(grid_s), dim3(kBlock), 0, s, a);
+        engine_grid_chunks(e, tiles_out + tiles_open, [&](uint32_t grid, uint64_t tb) {
+            hipLaunchKernelGGL(k_echo_emit, dim3(grid), dim3(kBlock), 0, s, a, tb, tiles_out);
+        });
+    }
+    return uvws_call_leave(e, prev, what);
+}
+
+int ec_check(uvhttp_ws_gpu_engine_t* e, const EcArgs& a, const char* null_msg, const char* align_msg,
+             const char* size_msg) {
+    if (!a.desc || !a.out_off || !a.open_off || !a.conn || !a.sum || (!a.wire && a.wire_len) ||
+        (!a.out && a.out_cap) || (a.streams ? !a.results : !a.bsum))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, null_msg);
+    if (((uintptr_t)a.wire & 15u) || ((uintptr_t)a.out & 15u) || ((uintptr_t)a.open & 15u) ||
+        ((uintptr_t)a.carry & 15u) || ((uintptr_t)a.desc & 7u) || ((uintptr_t)a.streams & 7u) ||
+        ((uintptr_t)a.results & 7u) || ((uintptr_t)a.bsum & 7u) || ((uintptr_t)a.out_off & 7u) ||
+        ((uintptr_t)a.carry_off & 7u) || ((uintptr_t)a.open_off & 7u) || ((uintptr_t)a.keys & 3u) ||
+        ((uintptr_t)a.runs & 3u) || ((uintptr_t)a.conn & 7u) || ((uintptr_t)a.sum & 7u))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, align_msg);
+    if (a.max_frames > (1u << 28) || a.max_echoes > (1u << 28) || a.n_streams > (1u << 31) ||
+        (a.runs && (a.run_stride < 8 || (a.run_stride & 3u))))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, size_msg);
+    return UVHTTP_WS_GPU_OK;
+}
+
+}  // namespace
+
+extern "C" int uvhttp_ws_gpu_echo_messages_streams(
+    uvhttp_ws_gpu_engine_t* e, const uint8_t* d_wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+    uint32_t max_frames, const uvhttp_ws_stream_t* d_streams, const uvhttp_ws_stream_result_t* d_results,
+    uint32_t n_streams, const uint8_t* d_enable, const uint32_t* d_mask_keys, uint32_t flags, const uint8_t* d_carry,
+    uint64_t carry_len, const uint64_t* d_carry_off, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+    uint32_t max_echoes, uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+    uint64_t* d_open_off, uvhttp_ws_echo_conn_t* d_conn, uvhttp_ws_echo_summary_t* d_summary, void* stream) {
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    if (!d_streams) return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, "echo_messages_streams: NULL argument");
+    EcArgs a = {};
+    a.wire = d_wire;
+    a.wire_len = wire_len;
+    a.desc = d_desc;
+    a.max_frames = max_frames;
+    a.n_streams = n_streams;
+    a.streams = d_streams;
+    a.results = d_results;
+    a.enable = d_enable;
+    a.keys = d_mask_keys;
+    a.flags = flags;
+    a.carry = d_carry;
+    a.carry_len = carry_len;
+    a.carry_off = d_carry_off;
+    a.out = d_out;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    a.max_echoes = max_echoes;
+    a.runs = d_runs;
+    a.run_stride = run_stride;
+    a.open = d_open;
+    a.open_cap = open_cap;
+    a.open_off = d_open_off;
+    a.conn = d_conn;
+    a.sum = d_summary;
+    const int rc = ec_check(e, a, "echo_messages_streams: NULL argument", "echo_messages_streams: misaligned argument",
+                            "echo_messages_streams: max_frames or max_echoes > 2^28, n_streams > 2^31 or a bad run_stride");
+    if (rc != UVHTTP_WS_GPU_OK) return rc;
+    return ec_run(e, a, stream, "echo_messages_streams launch");
+}
+
+extern "C" int uvhttp_ws_gpu_echo_messages_inplace(
+    uvhttp_ws_gpu_engine_t* e, const uint8_t* d_wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+    uint32_t n_frames, const uvhttp_ws_batch_summary_t* d_batch_summary, int32_t is_server,
+    const uint32_t* d_mask_keys, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+    uint32_t max_echoes, uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+    uint64_t* d_open_off, uvhttp_ws_echo_conn_t* d_conn, uvhttp_ws_echo_summary_t* d_summary, void* stream) {
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    EcArgs a = {};
+    a.wire = d_wire;
+    a.wire_len = wire_len;
+    a.desc = d_desc;
+    a.max_frames = n_frames;
+    a.n_streams = 1;
+    a.bsum = d_batch_summary;
+    a.is_server = is_server;
+    a.keys = d_mask_keys;
+    a.flags = flags;
+    a.out = d_out;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    a.max_echoes = max_echoes;
+    a.runs = d_runs;
+    a.run_stride = run_stride;
+    a.open = d_open;
+    a.open_cap = open_cap;
+    a.open_off = d_open_off;
+    a.conn = d_conn;
+    a.sum = d_summary;
+    const int rc = ec_check(e, a, "echo_messages_inplace: NULL argument", "echo_messages_inplace: misaligned argument",
+                            "echo_messages_inplace: n_frames or max_echoes > 2^28 or a bad run_stride");
+    if (rc != UVHTTP_WS_GPU_OK) return rc;
+    return ec_run(e, a, stream, "echo_messages_inplace launch");
+}

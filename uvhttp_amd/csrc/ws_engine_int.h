@@ -49,6 +49,8 @@ UVWS_INTERNAL void uvws_grid_note(uvhttp_ws_gpu_engine_t* e, uint64_t tiles, uin
 UVWS_INTERNAL void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 // The control replies' scratch (ws_replies_gpu.hip), likewise.
 UVWS_INTERNAL void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
+// The echo of data messages' scratch (ws_echo_gpu.hip), likewise.
+UVWS_INTERNAL void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"
 

@@ -5603,6 +5603,7 @@ enum ScratchId {
     kScrSp,       // the speculative stream decode's scratch (spec_layout(sp_streams, sp_tiles))
     kScrUtf8,     // the frame UTF-8 validator's (utf8_frames_gpu.hip; uvws_utf8_scratch)
     kScrReplies,  // the control replies' (ws_replies_gpu.hip; uvws_replies_scratch)
+    kScrEcho,     // the echo of data messages' (ws_echo_gpu.hip; uvws_echo_scratch)
     kScrCount
 };
 
@@ -6477,6 +6478,9 @@ void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s
 }
 void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
     return scratch_ptr(e, kScrReplies, bytes, s);
+}
+void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
+    return scratch_ptr(e, kScrEcho, bytes, s);
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot

@@ -808,3 +808,137 @@ int uvhttp_ws_control_replies(const uint8_t* wire, uint64_t wire_len,
     }
     return 0;
 }
+
+/* ---- echo of data messages: the echo server's frames of one connection's delivered frames -- */
+/* The host twin of uvhttp_ws_gpu_echo_messages_streams / _inplace and the statement of their
+ * rules (include/uvhttp_ws_amd.h): what on_message -> uvhttp_ws_send_text / _send_binary puts on
+ * the wire for every message whose FIN frame is delivered while state == OPEN, written as the
+ * frames uvhttp_ws_build_frame(..., opcode, mask = !is_server, fin = 1) makes of them, and the
+ * bytes of the message still open afterwards. */
+static int echo_is_data(const uvhttp_ws_frame_desc_t* d) {
+    return d->status == UVHTTP_WS_FRAME_OK && d->opcode <= UVHTTP_WS_OPCODE_BINARY;
+}
+
+/* the message's bytes in order — the carry when it was carried in (first == -1), then the data
+ * payloads of desc[lo, hi] — to dst, XOR-ed with the key from message offset 0 on */
+static void echo_gather(uint8_t* dst, const uint8_t* wire, const uvhttp_ws_frame_desc_t* desc,
+                        uint64_t lo, uint64_t hi, const uint8_t* carry, uint64_t carry_len,
+                        uint32_t key) {
+    uint64_t m = 0;
+    for (uint64_t b = 0; b < carry_len; ++b, ++m) dst[m] = (uint8_t)(carry[b] ^ (uint8_t)(key >> (8 * (m & 3))));
+    for (uint64_t i = lo; i <= hi; ++i) {
+        if (!echo_is_data(&desc[i])) continue;
+        const uint8_t* p = wire + desc[i].payload_off;
+        for (uint64_t b = 0; b < desc[i].payload_len; ++b, ++m)
+            dst[m] = (uint8_t)(p[b] ^ (uint8_t)(key >> (8 * (m & 3))));
+    }
+}
+
+int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
+                            const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                            uint32_t n_delivered, int is_server, int enable,
+                            const uint32_t* mask_keys, uint32_t flags, int pending_opcode,
+                            uint64_t pending_bytes, const uint8_t* carry, uint64_t carry_len,
+                            uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                            uint32_t max_echoes, uint8_t* open, uint64_t open_cap,
+                            uvhttp_ws_echo_conn_t* r) {
+    if (r == NULL || out_off == NULL || (desc == NULL && n_delivered != 0) ||
+        (wire == NULL && wire_len != 0) || (out == NULL && out_cap != 0) ||
+        (carry == NULL && carry_len != 0))
+        return -1;
+    memset(r, 0, sizeof(*r));
+    for (uint64_t j = 0; j <= max_echoes; ++j) out_off[j] = 0;
+    if (!enable) return 0; /* skipped as a whole */
+    const int masked = !is_server;
+    if (masked && mask_keys == NULL) {
+        r->status = UVHTTP_WS_ECHO_NO_KEYS;
+        return 0;
+    }
+    if (pending_bytes != 0 && carry_len != pending_bytes) {
+        r->status = UVHTTP_WS_ECHO_NO_CARRY;
+        return 0;
+    }
+    /* two passes over the same walk: size (and BAD_RANGE), then emit */
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t n = 0, bytes = 0;
+        int closed = 0;
+        /* the open message: is there one, its opcode, its length, whether it was carried in and
+         * the first descriptor that can hold a fragment of it */
+        int cur = pending_bytes != 0, cur_op = pending_opcode & 0x0F, carried = cur;
+        uint64_t cur_len = pending_bytes, lo = first_frame;
+        for (uint32_t i = 0; i < n_delivered; ++i) {
+            const uint64_t f = (uint64_t)first_frame + i;
+            const uvhttp_ws_frame_desc_t* d = &desc[f];
+            if (d->status != UVHTTP_WS_FRAME_OK) continue; /* not delivered */
+            if (d->opcode == UVHTTP_WS_OPCODE_CLOSE) closed = 1;
+            if (!echo_is_data(d)) continue;
+            if (pass == 0 && d->payload_len != 0 && !utf8_range_ok(wire_len, d->payload_off, d->payload_len)) {
+                r->status = UVHTTP_WS_ECHO_BAD_RANGE;
+                return 0;
+            }
+            if (d->opcode != UVHTTP_WS_OPCODE_CONTINUATION) {
+                cur = 1;
+                cur_op = d->opcode;
+                carried = 0;
+                cur_len = 0;
+                lo = f;
+            } else if (!cur) {
+                continue; /* a CONTINUATION of nothing */
+            }
+            cur_len += d->payload_len;
+            if (!(d->flags & UVHTTP_WS_FLAG_FIN)) continue;
+            cur = 0;
+            if (closed || ((flags & UVHTTP_WS_ECHO_SERVER_SEND) && cur_len == 0)) continue;
+            const uint64_t hdr = (cur_len <= 125 ? 2u : cur_len <= 65535 ? 4u : 10u) + (masked ? 4u : 0u);
+            if (pass == 1) {
+                uint8_t* o = out + bytes;
+                const uint32_t key = masked ? mask_keys[n] : 0u;
+                const int op = (flags & UVHTTP_WS_ECHO_SERVER_SEND) ? UVHTTP_WS_OPCODE_TEXT : cur_op;
+                uint64_t h = 2;
+                o[0] = (uint8_t)(0x80u | (unsigned)op);
+                if (cur_len <= 125) {
+                    o[1] = (uint8_t)cur_len;
+                } else if (cur_len <= 65535) {
+                    o[1] = 126;
+                    o[2] = (uint8_t)(cur_len >> 8);
+                    o[3] = (uint8_t)cur_len;
+                    h = 4;
+                } else {
+                    o[1] = 127;
+                    for (int k = 0; k < 8; ++k) o[2 + k] = (uint8_t)(cur_len >> (8 * (7 - k)));
+                    h = 10;
+                }
+                if (masked) {
+                    o[1] |= 0x80u;
+                    for (int k = 0; k < 4; ++k) o[h + k] = (uint8_t)(key >> (8 * k));
+                }
+                echo_gather(o + hdr, wire, desc, lo, f, carry, carried ? carry_len : 0, key);
+                out_off[n] = bytes;
+            }
+            n++;
+            bytes += hdr + cur_len;
+        }
+        if (!cur || cur_len == 0) {
+            cur = 0;
+            cur_len = 0;
+        }
+        if (pass == 0) {
+            r->n_echoes = (uint32_t)n;
+            r->out_len = bytes;
+            r->open_len = cur_len;
+            if (n > max_echoes || bytes > out_cap || (open != NULL && cur_len > open_cap)) {
+                r->status = UVHTTP_WS_ECHO_ERR_CAPACITY;
+                return 0;
+            }
+            r->open_opcode = (uint8_t)(cur ? cur_op : 0);
+        } else {
+            for (uint64_t j = n; j <= max_echoes; ++j) out_off[j] = bytes;
+            if (cur && open != NULL && n_delivered != 0)
+                echo_gather(open, wire, desc, lo, (uint64_t)first_frame + n_delivered - 1, carry,
+                            carried ? carry_len : 0, 0u);
+            else if (cur && open != NULL)
+                memcpy(open, carry, (size_t)carry_len);
+        }
+    }
+    return 0;
+}
