@@ -999,6 +999,116 @@ int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
                             uint32_t max_echoes, uint8_t* open, uint64_t open_cap,
                             uvhttp_ws_echo_conn_t* conn_result);
 
+/* ---- relay of data messages: the room server's broadcast built on the device after a decode - */
+/* The reference's other send path is uvhttp_server_ws_broadcast (src/uvhttp_server.c:1626-1657):
+ * every OPEN connection registered on a path gets the message as one TEXT frame; called from
+ * on_message it is the chat / pub-sub server.  This call builds, for a whole decoded batch, the
+ * frames of all messages completed in the batch grouped by room, and names every receiver its
+ * room's run where uvhttp_tls_gpu_seal_frames reads it ("one built frame, N sends with N keys"),
+ * so open_records -> ws_streams -> decode_reads -> relay_messages (+ control_replies) ->
+ * seal_frames needs no host read.  The fan-out costs no frame bytes: every member of a room names
+ * the same run.
+ *
+ * Frames considered, message membership, carry-in, NO_CARRY, which messages qualify (the FIN
+ * frame delivered, and not after the sender's first delivered CLOSE: a peer that sent CLOSE sends
+ * no more data, RFC 6455 section 5.5.1, and a room has one frame list), BAD_RANGE, d_enable and
+ * UVHTTP_WS_ECHO_SERVER_SEND are uvhttp_ws_gpu_echo_messages_streams' (above).  Under SERVER_SEND
+ * every frame is TEXT and an empty message gets none: uvhttp_server_ws_broadcast's send_text and
+ * its len == 0 refusal.
+ *
+ * Server frames.  A relayed frame is uvhttp_ws_build_frame(..., mask = 0, fin = 1), one per
+ * message, with a header of 2, 4 or 10 bytes; the sender's is_server plays no part, there is no
+ * key table and no NO_KEYS.
+ *
+ * Open messages.  d_open / d_open_off / open_len / open_opcode are per sender in connection
+ * index order, byte for byte what the echo writes: call k's open buffer is call k + 1's carry,
+ * whatever the rooms are.
+ *
+ * Rooms.  d_room[s] < n_rooms is sender s's room.  An enabled connection with d_room[s] >=
+ * n_rooms gets status UVHTTP_WS_RELAY_BAD_ROOM: no frames, open_len 0, counted in n_bad_rooms.
+ * The statuses rank NO_CARRY, else BAD_ROOM, else BAD_RANGE.
+ *
+ * Order.  Frames lie back to back in d_out ordered by (room, sender's connection index, frame
+ * order of the FIN frames).  d_out_off[j] starts frame j, and every entry from d_out_off[n_frames]
+ * to d_out_off[max_frames_out] equals the total: d_out / d_out_off with n_frames_total =
+ * max_frames_out is a valid uvhttp_tls_gpu_seal_frames input as it lies.  d_rooms[r] holds room
+ * r's run and byte range; a room with no frame gets n_frames 0, first_frame = the frames of the
+ * rooms before it, out_off = their bytes, out_len 0.  d_conn[s].first_echo / n_echoes / out_len
+ * name sender s's own frames inside that order; a connection with no frame gets first_echo = the
+ * frames before its place when all connections are ordered by (min(d_room[s], n_rooms), s).
+ *
+ * Receivers.  Receiver k gets d_rooms[d_recv_room[k]].first_frame and .n_frames at (char*)d_sends
+ * + k * send_stride: &sends[0].first_frame with stride sizeof(uvhttp_tls_send_t).  Every member
+ * is named, the sender included, as the reference's broadcast does; receivers need not be senders
+ * and senders need not be receivers.  d_recv_room[k] >= n_rooms gives (0, 0) and counts in
+ * n_bad_receivers.  d_sends and d_recv_room may be NULL with n_receivers = 0.
+ *
+ * Capacity, as for the echo: if the frames exceed max_frames_out, their bytes out_cap or (with
+ * d_open) the open bytes open_cap, nothing is written to d_out or d_open, all offsets, room
+ * entries and receiver runs are 0, every per-connection result is zero but for status
+ * ERR_CAPACITY, and the summary holds the three totals needed with status ERR_CAPACITY
+ * (n_bad_rooms and n_bad_receivers are counted either way).
+ *
+ * Pointers and alignment as for the echo; d_room, d_recv_room and d_sends 4, d_rooms 8.  EINVAL
+ * for NULL (d_enable, d_carry, d_carry_off and d_open excepted; d_rooms only with n_rooms = 0) or
+ * misaligned arguments, max_frames or max_frames_out > 2^28, n_streams > 2^31, n_rooms > 2^28,
+ * send_stride < 8 or not a multiple of 4; ENODEV without a device.  Asynchronous on `stream`
+ * under the engine's stream rule.  Scratch lives in the engine, shared with the echo (28 bytes
+ * per descriptor, 168 per connection, none per room, 64 per output slot, 4 per 64 KiB of out_cap
+ * and of open_cap, no epoch tags), grown on demand: graph-capturable once one uncaptured call of
+ * the same or a larger shape has been made; a captured call that would allocate fails with
+ * ENOMEM.  There is no in-place form: one connection has nobody to relay to. */
+#define UVHTTP_WS_RELAY_BAD_ROOM 5       /* per connection, beside UVHTTP_WS_ECHO_*: d_room[s] >= n_rooms */
+
+typedef struct {            /* 32 B, one per room, device-written */
+    uint32_t first_frame;   /* index of the room's first frame in d_out_off */
+    uint32_t n_frames;
+    uint64_t out_off;       /* its frames are d_out[out_off, out_off + out_len) */
+    uint64_t out_len;
+    uint64_t reserved;
+} uvhttp_ws_relay_room_t;
+
+typedef struct {            /* 32 B */
+    uint64_t out_bytes;     /* bytes of d_out the call needs */
+    uint64_t open_bytes;    /* bytes of d_open the call needs */
+    uint32_t n_frames;      /* frames the call needs */
+    int32_t status;         /* UVHTTP_WS_ECHO_OK or UVHTTP_WS_ECHO_ERR_CAPACITY */
+    uint32_t n_bad_rooms;   /* enabled connections with status BAD_ROOM */
+    uint32_t n_bad_receivers;
+} uvhttp_ws_relay_summary_t;
+
+int uvhttp_ws_gpu_relay_messages_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                         uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                         uint32_t max_frames, const uvhttp_ws_stream_t* d_streams,
+                                         const uvhttp_ws_stream_result_t* d_results,
+                                         uint32_t n_streams, const uint8_t* d_enable,
+                                         const uint32_t* d_room, uint32_t n_rooms, uint32_t flags,
+                                         const uint8_t* d_carry, uint64_t carry_len,
+                                         const uint64_t* d_carry_off, uint8_t* d_out,
+                                         uint64_t out_cap, uint64_t* d_out_off,
+                                         uint32_t max_frames_out, uvhttp_ws_relay_room_t* d_rooms,
+                                         const uint32_t* d_recv_room, uint32_t n_receivers,
+                                         uint32_t* d_sends, uint32_t send_stride, uint8_t* d_open,
+                                         uint64_t open_cap, uint64_t* d_open_off,
+                                         uvhttp_ws_echo_conn_t* d_conn,
+                                         uvhttp_ws_relay_summary_t* d_summary, void* stream);
+/* Host twin (plain C, host copies of the same tables): all connections of the call at once and
+ * the same outputs, byte for byte; the statement of the rules.  Returns 0, or -1 for NULL
+ * arguments (as above; desc may be NULL when max_frames is 0, out when out_cap is 0) or when it
+ * cannot allocate its temporaries. */
+int uvhttp_ws_relay_messages(const uint8_t* wire, uint64_t wire_len,
+                             const uvhttp_ws_frame_desc_t* desc, uint32_t max_frames,
+                             const uvhttp_ws_stream_t* streams,
+                             const uvhttp_ws_stream_result_t* results, uint32_t n_streams,
+                             const uint8_t* enable, const uint32_t* room, uint32_t n_rooms,
+                             uint32_t flags, const uint8_t* carry, uint64_t carry_len,
+                             const uint64_t* carry_off, uint8_t* out, uint64_t out_cap,
+                             uint64_t* out_off, uint32_t max_frames_out,
+                             uvhttp_ws_relay_room_t* rooms, const uint32_t* recv_room,
+                             uint32_t n_receivers, uint32_t* sends, uint32_t send_stride,
+                             uint8_t* open, uint64_t open_cap, uint64_t* open_off,
+                             uvhttp_ws_echo_conn_t* conn, uvhttp_ws_relay_summary_t* summary);
+
 /* ---- host-memory pipeline (libuv read buffers in, decoded payloads out) ---------------- */
 /* A pipeline owns `depth` slots.  Each slot = a pinned host staging buffer (the caller
  * writes masked frames there, e.g. hands it out from the libuv alloc callback) and a device

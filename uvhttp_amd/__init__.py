@@ -162,6 +162,28 @@ class EchoSummary(C.Structure):
         return {k: getattr(self, k) for k in ("out_bytes", "open_bytes", "n_echoes", "status")}
 
 
+RELAY_BAD_ROOM = 5  # UVHTTP_WS_RELAY_BAD_ROOM, beside the ECHO_* statuses
+
+
+class RelayRoom(C.Structure):
+    """uvhttp_ws_relay_room_t (32 B)."""
+    _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("out_off", C.c_uint64),
+                ("out_len", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("first_frame", "n_frames", "out_off", "out_len")}
+
+
+class RelaySummary(C.Structure):
+    """uvhttp_ws_relay_summary_t (32 B)."""
+    _fields_ = [("out_bytes", C.c_uint64), ("open_bytes", C.c_uint64), ("n_frames", C.c_uint32),
+                ("status", C.c_int32), ("n_bad_rooms", C.c_uint32), ("n_bad_receivers", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("out_bytes", "open_bytes", "n_frames", "status", "n_bad_rooms",
+                                              "n_bad_receivers")}
+
+
 class Stream(C.Structure):
     """uvhttp_ws_stream_t (64 B)."""
     _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("recv_buffer_size", C.c_uint64),
@@ -406,6 +428,11 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_ws_echo_messages": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, C.c_int,
                                               u64, vp, u64, vp, u64, vp, u32, vp, u64,
                                               C.POINTER(EchoConn)]),
+        "uvhttp_ws_gpu_relay_messages_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u32,
+                                                           vp, u64, vp, vp, u64, vp, u32, vp, vp, u32, vp,
+                                                           u32, vp, u64, vp, vp, vp, vp]),
+        "uvhttp_ws_relay_messages": (C.c_int, [vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u32, vp, u64, vp,
+                                               vp, u64, vp, u32, vp, vp, u32, vp, u32, vp, u64, vp, vp, vp]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -645,6 +672,48 @@ def echo_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, m
     ok = res.status != ECHO_ERR_CAPACITY
     return (bytes(out)[: res.out_len if ok else 0], list(off),
             bytes(opn)[: res.open_len if ok else 0] if want_open else b"", res.as_dict())
+
+
+def relay_messages(wire, desc, max_frames, streams, results, room, n_rooms, enable=None, flags=0,
+                   carry=None, carry_off=None, recv_room=(), out_cap=None, max_frames_out=None,
+                   open_cap=None, want_open=True, wire_len=None):
+    """uvhttp_ws_relay_messages: the host twin of GpuEngine.relay_messages_streams over host
+    copies of the same tables.  `wire` / `desc` / `streams` / `results` = numpy arrays or bytes (the
+    64-byte uvhttp_ws_stream_t and uvhttp_ws_stream_result_t tables), room / recv_room / enable =
+    sequences, carry = bytes with carry_off = its n_streams + 1 offsets.  The capacities default
+    to what the call can need.  -> dict: out, out_off [max_frames_out + 1], open, open_off
+    [n_streams + 1], conn [EchoConn.as_dict()], rooms [RelayRoom.as_dict()], sends [(first_frame,
+    n_frames)], summary (RelaySummary.as_dict())."""
+    wb, db, sb, rb = _host_buf(wire), _host_buf(desc), _host_buf(streams), _host_buf(results)
+    S = len(room)
+    n = len(wire) if wire_len is None else wire_len
+    carry = b"" if carry is None else bytes(carry)
+    max_frames_out = max_frames if max_frames_out is None else max_frames_out
+    out_cap = 10 * max_frames + n + len(carry) if out_cap is None else out_cap
+    open_cap = n + len(carry) if open_cap is None else open_cap
+    out = (C.c_uint8 * max(1, out_cap))()
+    opn = (C.c_uint8 * max(1, open_cap))() if want_open else None
+    off = (C.c_uint64 * (max_frames_out + 1))()
+    ooff = (C.c_uint64 * (S + 1))()
+    rm = (C.c_uint32 * max(1, S))(*room)
+    en = None if enable is None else (C.c_uint8 * max(1, S))(*enable)
+    cb = (C.c_uint8 * max(1, len(carry))).from_buffer_copy(carry or b"\0")
+    co = None if carry_off is None else (C.c_uint64 * (S + 1))(*carry_off)
+    rooms = (RelayRoom * max(1, n_rooms))()
+    rr = (C.c_uint32 * max(1, len(recv_room)))(*recv_room)
+    sends = (C.c_uint32 * max(2, 2 * len(recv_room)))()
+    conn = (EchoConn * max(1, S))()
+    summ = RelaySummary()
+    rc = lib().uvhttp_ws_relay_messages(wb, n, db, max_frames, sb, rb, S, en, rm, n_rooms, flags, cb, len(carry), co,
+                                        out, out_cap, off, max_frames_out, rooms, rr, len(recv_room), sends, 8, opn,
+                                        open_cap, ooff, conn, C.byref(summ))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_relay_messages: bad argument")
+    ok = summ.status != ECHO_ERR_CAPACITY
+    return {"out": bytes(out)[: summ.out_bytes if ok else 0], "out_off": list(off),
+            "open": bytes(opn)[: summ.open_bytes if ok else 0] if want_open else b"", "open_off": list(ooff),
+            "conn": [conn[s].as_dict() for s in range(S)], "rooms": [rooms[r].as_dict() for r in range(n_rooms)],
+            "sends": [(sends[2 * k], sends[2 * k + 1]) for k in range(len(recv_room))], "summary": summ.as_dict()}
 
 
 class WsConnection:
@@ -1126,6 +1195,46 @@ class GpuEngine:
             open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
             C.c_void_p(summary.data_ptr()), self._stream(stream)), "echo_messages_inplace")
         return out, out_off, open_off, conn, summary
+
+    def relay_messages_streams(self, wire, desc, max_frames, streams_dev, results, n_streams, room,
+                               n_rooms, max_frames_out, out_cap, enable=None, flags=0, carry=None,
+                               carry_len=0, carry_off=None, out=None, out_off=None, rooms=None,
+                               recv_room=None, n_receivers=0, sends=None, send_stride=8, open=None,
+                               open_cap=0, open_off=None, conn=None, summary=None, wire_len=None,
+                               stream=None):
+        """uvhttp_ws_gpu_relay_messages_streams after decode_streams / decode_reads over the same
+        device tensors: one server frame per data message whose FIN frame was delivered, laid out
+        by (room, connection); room = n_streams uint32 on the device, rooms = n_rooms 32-byte
+        uvhttp_ws_relay_room_t, recv_room / sends = the receivers' rooms and where their
+        (first_frame, n_frames) go (send_stride bytes apart; None with n_receivers = 0).  The rest
+        as echo_messages_streams.  Returns (out, out_off, open_off, conn, rooms, summary)."""
+        out, out_off, open_off, conn, summary = self._echo_out(n_streams, max_frames_out, out_cap, out,
+                                                               out_off, open_off, conn, summary)
+        if rooms is None:
+            rooms = self.torch.zeros(max(1, n_rooms) * C.sizeof(RelayRoom), dtype=self.torch.uint8,
+                                     device=f"cuda:{self.device}")
+        self._check(self._L.uvhttp_ws_gpu_relay_messages_streams(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), max_frames, C.c_void_p(streams_dev.data_ptr()),
+            C.c_void_p(results.data_ptr()), n_streams, self._ptr(enable), C.c_void_p(room.data_ptr()), n_rooms,
+            flags, self._ptr(carry), carry_len, self._ptr(carry_off), C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_frames_out, C.c_void_p(rooms.data_ptr()), self._ptr(recv_room),
+            n_receivers, self._ptr(sends), send_stride, self._ptr(open), open_cap,
+            C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()), C.c_void_p(summary.data_ptr()),
+            self._stream(stream)), "relay_messages_streams")
+        return out, out_off, open_off, conn, rooms, summary
+
+    @staticmethod
+    def read_relay_rooms(rooms, n):
+        """host copy of the first n room entries -> [dict] (RelayRoom.as_dict)"""
+        sz = C.sizeof(RelayRoom)
+        raw = bytes(rooms[: n * sz].cpu().numpy().tobytes())
+        return [RelayRoom.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_relay_summary(summary) -> dict:
+        raw = bytes(summary.cpu().numpy().tobytes())
+        return RelaySummary.from_buffer_copy(raw).as_dict()
 
     @staticmethod
     def read_echo_conns(conn, n):

@@ -54,7 +54,26 @@
 // the n_streams entries, d_out below out_cap, d_open below open_cap and the offset tables is read
 // or written: every source frame is one whose range k_echo_classify checked, and the emit is
 // bounded by the totals the capacity test used.
+//
+// The relay (uvhttp_ws_gpu_relay_messages_streams) is the same sizing and the same emit with
+// another order: server frames laid out by (room, connection, frame).  Nothing in the emit depends
+// on descriptor order, only on records that ascend in their destination by output slot, so what
+// is added lies between k_echo_size and the record writes:
+//
+//   k_echo_offsets  run once for the connections' counts and bytes only (cbeg .. bend)
+//   k_relay_hist / _hreduce / k_echo_top / k_relay_hscan / k_relay_scatter   per 8 bits of n_rooms:
+//                   the connections sorted by (min(room, n_rooms), index), see "the relay's order"
+//   k_relay_oreduce / k_echo_top x 2 / k_relay_obase   counts and bytes scanned in that order:
+//                   every connection's first slot and offset, and the sums by place for the rooms
+//   k_echo_offsets  again: each record, d_out_off[j] and the tile map at the connection's base
+//   k_relay_rooms   one lane per room: two searches over the sorted keys, d_rooms[r]
+//   k_relay_recv    one lane per receiver: its room's run
+//
+// The kernels both calls use and the relay changes (init, conns, size, offsets, finish, emit) are
+// templates over the argument type, EcArgs or RlArgs: the echo's instances are the kernels they
+// were, launched as they were, and only the relay's carry the room order and its arguments.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "uvhttp_ws_amd.h"
@@ -159,6 +178,36 @@ struct EcArgs {
     EcRec* orec;            // [n_streams] the open messages' records
     uint32_t* tmap;         // [tiles of d_out] the record that holds the tile's first byte
     uint32_t* omap;         // [tiles of d_open] likewise
+    static constexpr bool kRelay = false;
+};
+
+// The relay's arguments (uvhttp_ws_gpu_relay_messages_streams): the echo's and its own.  The
+// kernels both calls share are templates over the argument type, so the echo's instances are the
+// kernels they were, with the arguments they had.
+struct RlArgs : EcArgs {
+    static constexpr bool kRelay = true;  // server frames in (room, connection) order
+    uint32_t count_only;        // k_echo_offsets: the connections' counts and bytes, nothing else
+    const uint32_t* room;       // [n_streams] the sender's room
+    uint32_t n_rooms;
+    uint32_t n_receivers;
+    uvhttp_ws_relay_room_t* rooms;  // [n_rooms]
+    const uint32_t* recv_room;  // [n_receivers]
+    uint32_t* sends;            // (first_frame, n_frames) per receiver, send_stride bytes apart
+    uint32_t send_stride;
+    // ... its scratch
+    uint32_t* skey[2];      // [n_streams] sort keys min(room, n_rooms), in and out of a radix pass
+    uint32_t* sidx[2];      // [n_streams] the connections that go with them
+    const uint32_t* okey;   // the sorted keys and connections: skey / sidx [passes & 1]
+    const uint32_t* oidx;
+    uint32_t* hist;         // [256 digits][connection blocks] digit counts, then exclusive sums
+    uint64_t* agg_h;        // [connection blocks] sums of 256 hist entries, then inclusive
+    uint64_t* agg_pc;       // [connection blocks] frames of 256 places of the order, then inclusive
+    uint64_t* agg_pb;       // the same in bytes
+    uint64_t* pcnt;         // [n_streams + 1] frames before place p of the order; the last: all
+    uint64_t* pbytes;       // the same in bytes
+    uint32_t* rcnt;         // [n_streams] pcnt at the connection's place: its first frame's slot
+    uint64_t* rbytes;       // likewise its first frame's offset
+    uint32_t* written;      // [1] records k_echo_offsets wrote: the emit runs only when all were
 };
 
 struct LastOp {  // the later mark
@@ -220,11 +269,25 @@ __device__ __forceinline__ EcRange conn_range(const EcArgs& a, uint32_t s) {
 __device__ __forceinline__ bool conn_server(const EcArgs& a, uint32_t s) {
     return a.streams ? a.streams[s].is_server != 0 : a.is_server != 0;
 }
+// whether the connection's output frames are masked: a client's echoes; relayed frames never are
+template <class A>
+__device__ __forceinline__ bool conn_masked(const A& a, uint32_t s) {
+    return !A::kRelay && !conn_server(a, s);
+}
 __device__ __forceinline__ uint64_t conn_pending(const EcArgs& a, uint32_t s) {
     return a.streams ? a.streams[s].pending_bytes : 0;
 }
 __device__ __forceinline__ uint32_t conn_pending_opcode(const EcArgs& a, uint32_t s) {
     return a.streams ? (uint32_t)a.streams[s].pending_opcode & 0x0Fu : 0u;
+}
+
+// the connection's frames and their bytes, after k_echo_offsets (0 where a broken table left its
+// end before its beginning)
+__device__ __forceinline__ uint64_t conn_frames(const EcArgs& a, uint32_t s) {
+    return a.cend[s] >= a.cbeg[s] ? a.cend[s] - a.cbeg[s] : 0u;
+}
+__device__ __forceinline__ uint64_t conn_bytes(const EcArgs& a, uint32_t s) {
+    return a.bend[s] >= a.bbeg[s] ? a.bend[s] - a.bbeg[s] : 0u;
 }
 
 // the three totals and the capacity test every writer goes by
@@ -245,17 +308,20 @@ __device__ __forceinline__ uint32_t header_bytes(uint64_t len, bool masked) {
     return (len <= 125 ? 2u : len <= 65535 ? 4u : 10u) + (masked ? 4u : 0u);
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_init(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_init(A a) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i == 0) {
         uvhttp_ws_echo_summary_t z = {};
         *a.sum = z;
         a.open_off[0] = 0;
+        if constexpr (A::kRelay) *a.written = 0;
     }
     if (i < a.max_frames) a.marks[i] = 0;
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_conns(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_conns(A a) {
     const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= a.n_streams) return;
     a.first_close[s] = kNone;
@@ -268,7 +334,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_conns(EcArgs a) {
     uint32_t st = 0;
     const uint64_t pend = conn_pending(a, (uint32_t)s);
     if (!a.enable || a.enable[s] != 0) {
-        if (!conn_server(a, (uint32_t)s) && !a.keys) {
+        if (conn_masked(a, (uint32_t)s) && !a.keys) {
             st = UVHTTP_WS_ECHO_NO_KEYS;
         } else if (pend != 0) {
             bool usable = false;
@@ -280,6 +346,17 @@ __global__ __launch_bounds__(kBlock) void k_echo_conns(EcArgs a) {
         } else {
             st = kCActive;
         }
+        if constexpr (A::kRelay) {
+            if ((st & kCActive) && a.room[s] >= a.n_rooms) {  // after NO_CARRY, before BAD_RANGE
+                st = UVHTTP_WS_RELAY_BAD_ROOM;
+                atomicAdd(&a.sum->reserved[0], 1u);  // uvhttp_ws_relay_summary_t: n_bad_rooms
+            }
+        }
+    }
+    if constexpr (A::kRelay) {  // the radix sort's input: every connection, in its room or after the last
+        const uint32_t room = a.room[s];
+        a.skey[0][s] = room < a.n_rooms ? room : a.n_rooms;
+        a.sidx[0][s] = (uint32_t)s;
     }
     a.cstate[s] = st;
     const EcRange r = conn_range(a, (uint32_t)s);
@@ -404,7 +481,8 @@ __device__ __forceinline__ uint64_t message_len(const EcArgs& a, uint64_t v, uin
     return a.dsum[f] + plen - a.dsum[g] + ((v & 3) == kMsgCarried ? conn_pending(a, conn) : 0);
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_size(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_size(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint64_t e = f < a.max_frames ? a.elem[f] : 0;
@@ -419,7 +497,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_size(EcArgs a) {
             if ((uint32_t)f < a.first_close[conn] && !((a.flags & UVHTTP_WS_ECHO_SERVER_SEND) && len == 0)) {
                 e |= kEcho;
                 a.elem[f] = e;
-                bytes = header_bytes(len, !conn_server(a, conn)) + len;
+                bytes = header_bytes(len, conn_masked(a, conn)) + len;
             }
         }
         if ((e & kLast) && in_msg && !((e & kData) && (e & kFin))) {
@@ -445,7 +523,8 @@ __device__ __forceinline__ void map_tiles(uint32_t* map, uint32_t j, uint64_t o,
     for (uint64_t t = (o + kTile - 1) / kTile; t * kTile < o + n; ++t) map[t] = j;
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_offsets(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t e = f < a.max_frames ? a.elem[f] : 0;
@@ -456,13 +535,15 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(EcArgs a) {
     if (echo) {
         v = a.view[f];
         len = message_len(a, v, f, a.desc[f].payload_len, conn);
-        masked = !conn_server(a, conn);
+        masked = conn_masked(a, conn);
         mine = header_bytes(len, masked) + len;
     }
     uint64_t tot;
     const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + block_scan(echo ? 1 : 0, AddOp(), s_wave, &tot);
     const uint64_t bytes = (blockIdx.x ? a.agg_bytes[blockIdx.x - 1] : 0) + block_scan(mine, AddOp(), s_wave, &tot);
-    if (e & kIn) {
+    bool bounds = (e & kIn) != 0;
+    if constexpr (A::kRelay) bounds = bounds && a.count_only;  // (the relay's second run reads them)
+    if (bounds) {
         if (e & kFirst) {
             a.cbeg[conn] = (uint32_t)(cnt - (echo ? 1 : 0));
             a.bbeg[conn] = bytes - mine;
@@ -473,9 +554,25 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(EcArgs a) {
         }
     }
     if (!echo || !totals(a).fits) return;
-    const uint64_t j = cnt - 1, g = (v >> 2) - 1;
+    // slot and offset: the running totals, or (the relay) the connection's own place in the room
+    // order plus its frames before this one
+    uint64_t j = cnt - 1, at = bytes - mine;
+    if constexpr (A::kRelay) {
+        if (a.count_only) return;
+        // (a table whose ranges overlap can break a connection's counts: stay inside its own
+        // slots and the totals, and let the emit see that a slot was left out)
+        const uint64_t k = j - a.cbeg[conn], kb = at - a.bbeg[conn];
+        const EcTotals t = totals(a);
+        j = a.rcnt[conn] + k;
+        at = a.rbytes[conn] + kb;
+        if (k >= conn_frames(a, conn) || kb > conn_bytes(a, conn) || mine > conn_bytes(a, conn) - kb || j >= t.cnt ||
+            at > t.bytes || mine > t.bytes - at)
+            return;
+        atomicAdd(a.written, 1u);
+    }
+    const uint64_t g = (v >> 2) - 1;
     const bool carried = (v & 3) == kMsgCarried;
-    a.out_off[j] = bytes - mine;
+    a.out_off[j] = at;
     EcRec r;
     r.dbase = a.dsum[g];
     r.len = len;
@@ -493,7 +590,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(EcArgs a) {
     r.src0 = a.desc[f].payload_off;
     r.pad = 0;
     a.rec[j] = r;
-    map_tiles(a.tmap, (uint32_t)j, bytes - mine, mine);
+    map_tiles(a.tmap, (uint32_t)j, at, mine);
 }
 
 __global__ __launch_bounds__(kBlock) void k_echo_tail(EcArgs a) {
@@ -515,14 +612,15 @@ __global__ __launch_bounds__(kBlock) void k_echo_creduce(EcArgs a, int which) {
     if (threadIdx.x == 0) (which ? a.agg_co : a.agg_cn)[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_finish(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_finish(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = s < a.n_streams;
     const uint32_t n = live ? a.cend[s] - a.cbeg[s] : 0;
     const uint64_t ol = live ? a.olen[s] : 0;
-    uint64_t tot;
-    const uint64_t inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
+    uint64_t tot, inc_n = 0;  // (the relay has every connection's first slot already)
+    if constexpr (!A::kRelay) inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
     const uint64_t inc_o = (blockIdx.x ? a.agg_co[blockIdx.x - 1] : 0) + block_scan(ol, AddOp(), s_wave, &tot);
     const EcTotals t = totals(a);
     if (live) {
@@ -535,7 +633,8 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(EcArgs a) {
             const uint32_t cs = a.cstate[s];
             const uint64_t om = a.omark[s];
             const uint32_t kind = (uint32_t)(om & 3);
-            r.first_echo = (uint32_t)(inc_n - n);
+            if constexpr (A::kRelay) r.first_echo = a.rcnt[s];
+            else r.first_echo = (uint32_t)(inc_n - n);
             r.n_echoes = n;
             r.out_len = a.bend[s] - a.bbeg[s];
             r.open_len = ol;
@@ -573,6 +672,159 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(EcArgs a) {
         a.sum->n_echoes = (uint32_t)t.cnt;
         a.sum->status = t.fits ? UVHTTP_WS_ECHO_OK : UVHTTP_WS_ECHO_ERR_CAPACITY;
     }
+}
+
+// ---- the relay's order -----------------------------------------------------------------------------
+// The connections sorted by (min(room, n_rooms), index): a least-significant-digit radix sort of
+// 8 bits a pass over the bits n_rooms needs.  A pass is k_relay_hist (a workgroup's 256 keys ->
+// its count per digit, stored digit-major, so that one exclusive scan of the whole table gives
+// every (digit, workgroup) its base), the scan (k_relay_hreduce, k_echo_top, k_relay_hscan) and
+// k_relay_scatter, which ranks a key among the equal digits before it in its workgroup: stable,
+// so equal rooms keep index order.  Every kernel takes the first workgroup of its piece.
+
+__global__ __launch_bounds__(kBlock) void k_relay_hist(RlArgs a, uint64_t base, uint32_t shift, int from) {
+    __shared__ uint32_t s_h[kBlock];
+    const uint64_t b = base + blockIdx.x, nblk = ((uint64_t)a.n_streams + kBlock - 1) / kBlock;
+    const uint64_t p = b * kBlock + threadIdx.x;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    if (p < a.n_streams) atomicAdd(&s_h[(a.skey[from][p] >> shift) & 255u], 1u);
+    __syncthreads();
+    a.hist[(uint64_t)threadIdx.x * nblk + b] = s_h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kBlock) void k_relay_hreduce(RlArgs a, uint64_t base) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t b = base + blockIdx.x;
+    uint64_t tot;
+    (void)block_scan(a.hist[b * kBlock + threadIdx.x], AddOp(), s_wave, &tot);
+    if (threadIdx.x == 0) a.agg_h[b] = tot;
+}
+
+__global__ __launch_bounds__(kBlock) void k_relay_hscan(RlArgs a, uint64_t base) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t b = base + blockIdx.x;
+    const uint32_t v = a.hist[b * kBlock + threadIdx.x];
+    uint64_t tot;
+    const uint64_t inc = (b ? a.agg_h[b - 1] : 0) + block_scan(v, AddOp(), s_wave, &tot);
+    a.hist[b * kBlock + threadIdx.x] = (uint32_t)(inc - v);
+}
+
+__global__ __launch_bounds__(kBlock) void k_relay_scatter(RlArgs a, uint64_t base, uint32_t shift, int from) {
+    __shared__ uint32_t s_cnt[kWaves][kBlock];
+    const uint64_t b = base + blockIdx.x, nblk = ((uint64_t)a.n_streams + kBlock - 1) / kBlock;
+    const uint64_t p = b * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) s_cnt[k][threadIdx.x] = 0;
+    const bool live = p < a.n_streams;
+    const uint32_t key = live ? a.skey[from][p] : 0u, idx = live ? a.sidx[from][p] : 0u;
+    const uint32_t d = (key >> shift) & 255u;
+    uint64_t peers = __ballot(live);  // the wave's live lanes with this lane's digit
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+        const bool set = (d >> bit) & 1u;
+        const uint64_t m = __ballot(live && set);
+        peers &= set ? m : ~m;
+    }
+    const uint32_t below = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
+    __syncthreads();
+    if (live && below == 0) s_cnt[w][d] = (uint32_t)__popcll(peers);
+    __syncthreads();
+    if (!live) return;
+    uint32_t rank = below;
+    for (int k = 0; k < w; ++k) rank += s_cnt[k][d];
+    const uint64_t to = (uint64_t)a.hist[(uint64_t)d * nblk + b] + rank;
+    a.skey[from ^ 1][to] = key;
+    a.sidx[from ^ 1][to] = idx;
+}
+
+// frames and bytes of the connection at place p of the order
+__device__ __forceinline__ void place_sizes(const RlArgs& a, uint64_t p, uint32_t* s, uint64_t* n, uint64_t* bytes) {
+    *s = 0;
+    *n = *bytes = 0;
+    if (p >= a.n_streams) return;
+    *s = a.oidx[p];
+    *n = conn_frames(a, *s);
+    *bytes = conn_bytes(a, *s);
+}
+
+__global__ __launch_bounds__(kBlock) void k_relay_oreduce(RlArgs a, uint64_t base) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t b = base + blockIdx.x;
+    uint32_t s;
+    uint64_t n, bytes, tot_n, tot_b;
+    place_sizes(a, b * kBlock + threadIdx.x, &s, &n, &bytes);
+    (void)block_scan(n, AddOp(), s_wave, &tot_n);
+    (void)block_scan(bytes, AddOp(), s_wave, &tot_b);
+    if (threadIdx.x == 0) {
+        a.agg_pc[b] = tot_n;
+        a.agg_pb[b] = tot_b;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_relay_obase(RlArgs a, uint64_t base) {
+    __shared__ uint64_t s_wave[kWaves];
+    const uint64_t b = base + blockIdx.x, p = b * kBlock + threadIdx.x;
+    uint32_t s;
+    uint64_t n, bytes, tot;
+    place_sizes(a, p, &s, &n, &bytes);
+    const uint64_t inc_n = (b ? a.agg_pc[b - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
+    const uint64_t inc_b = (b ? a.agg_pb[b - 1] : 0) + block_scan(bytes, AddOp(), s_wave, &tot);
+    if (p >= a.n_streams) return;
+    a.pcnt[p] = inc_n - n;
+    a.pbytes[p] = inc_b - bytes;
+    a.rcnt[s] = (uint32_t)(inc_n - n);
+    a.rbytes[s] = inc_b - bytes;
+    if (p == (uint64_t)a.n_streams - 1) {
+        a.pcnt[p + 1] = inc_n;
+        a.pbytes[p + 1] = inc_b;
+    }
+}
+
+// the first place of the order whose key is >= x
+__device__ __forceinline__ uint64_t first_ge(const uint32_t* keys, uint64_t n, uint32_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one lane per room: its run of frames and their bytes from the places where its key begins and
+// ends, senders or not (all 0 on capacity)
+__global__ __launch_bounds__(kBlock) void k_relay_rooms(RlArgs a, uint64_t base) {
+    const uint64_t r = (base + blockIdx.x) * kBlock + threadIdx.x;
+    if (r >= a.n_rooms) return;
+    uvhttp_ws_relay_room_t o = {};
+    if (a.n_streams != 0 && totals(a).fits) {
+        const uint64_t lo = first_ge(a.okey, a.n_streams, (uint32_t)r);
+        const uint64_t hi = first_ge(a.okey, a.n_streams, (uint32_t)r + 1);
+        o.first_frame = (uint32_t)a.pcnt[lo];
+        o.n_frames = (uint32_t)(a.pcnt[hi] - a.pcnt[lo]);
+        o.out_off = a.pbytes[lo];
+        o.out_len = a.pbytes[hi] - a.pbytes[lo];
+    }
+    a.rooms[r] = o;
+}
+
+// one lane per receiver: its room's run where uvhttp_tls_gpu_seal_frames reads it
+__global__ __launch_bounds__(kBlock) void k_relay_recv(RlArgs a, uint64_t base) {
+    const uint64_t k = (base + blockIdx.x) * kBlock + threadIdx.x;
+    if (k >= a.n_receivers) return;
+    uint32_t first = 0, n = 0;
+    const uint32_t r = a.recv_room[k];
+    if (r < a.n_rooms) {
+        first = a.rooms[r].first_frame;
+        n = a.rooms[r].n_frames;
+    } else {
+        atomicAdd(&a.sum->reserved[1], 1u);  // uvhttp_ws_relay_summary_t: n_bad_receivers
+    }
+    uint32_t* run = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.sends) + k * a.send_stride);
+    run[0] = first;
+    run[1] = n;
 }
 
 // ---- the emit ------------------------------------------------------------------------------------
@@ -686,9 +938,13 @@ __device__ __forceinline__ void emit_vector(const EcArgs& a, const EcDst& o, uin
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_emit(EcArgs a, uint64_t tile_base, uint64_t tiles_out) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_emit(A a, uint64_t tile_base, uint64_t tiles_out) {
     const EcTotals t = totals(a);
     if (!t.fits) return;
+    if constexpr (A::kRelay) {
+        if (*a.written != t.cnt) return;  // (a broken table left a slot without its record)
+    }
     uint64_t tile = tile_base + blockIdx.x;
     const bool to_open = tile >= tiles_out;
     if (to_open) tile -= tiles_out;
@@ -794,7 +1050,9 @@ __global__ __launch_bounds__(kBlock) void k_echo_emit(EcArgs a, uint64_t tile_ba
 
 size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
 
-int ec_run(uvhttp_ws_gpu_engine_t* e, EcArgs a, void* stream, const char* what) {
+template <class A>
+int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
+    constexpr bool relay = A::kRelay;
     static_assert(sizeof(uvhttp_ws_echo_conn_t) == 32 && sizeof(uvhttp_ws_echo_summary_t) == 32, "ABI");
     const uint64_t F = a.max_frames, S = a.n_streams, E = a.max_echoes;
     const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
@@ -817,6 +1075,16 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, EcArgs a, void* stream, const char* what) 
     const size_t o_tmap = take((tiles_out + 1) * 4), o_omap = take((tiles_open + 1) * 4);
     const size_t o_cstate = take(S * 4), o_close = take(S * 4), o_bad = take(S * 4);
     const size_t o_cbeg = take(S * 4), o_cend = take(S * 4), o_ofend = take(S * 4);
+    // the relay's (nothing for the echo)
+    const uint64_t R = relay ? 1 : 0;
+    const size_t o_pcnt = take(R * (S + 1) * 8), o_pbytes = take(R * (S + 1) * 8), o_rbytes = take(R * S * 8);
+    const size_t o_aggh = take(R * ns * 8), o_aggpc = take(R * ns * 8), o_aggpb = take(R * ns * 8);
+    const size_t o_skey0 = take(R * S * 4), o_skey1 = take(R * S * 4), o_sidx0 = take(R * S * 4), o_sidx1 = take(R * S * 4);
+    const size_t o_hist = take(R * ns * kBlock * 4), o_rcnt = take(R * S * 4), o_written = take(R * 4);
+    // radix passes: the bits of the largest key, n_rooms
+    uint32_t passes = 0;
+    if constexpr (relay)
+        for (uint64_t top = a.n_rooms; top; top >>= 8) ++passes;
 
     hipStream_t s = (hipStream_t)stream;
     const int prev = uvws_call_enter(e, s);
@@ -850,37 +1118,98 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, EcArgs a, void* stream, const char* what) 
     a.cbeg = reinterpret_cast<uint32_t*>(mem + o_cbeg);
     a.cend = reinterpret_cast<uint32_t*>(mem + o_cend);
     a.ofend = reinterpret_cast<uint32_t*>(mem + o_ofend);
+    if constexpr (relay) {
+        a.pcnt = reinterpret_cast<uint64_t*>(mem + o_pcnt);
+        a.pbytes = reinterpret_cast<uint64_t*>(mem + o_pbytes);
+        a.rbytes = reinterpret_cast<uint64_t*>(mem + o_rbytes);
+        a.agg_h = reinterpret_cast<uint64_t*>(mem + o_aggh);
+        a.agg_pc = reinterpret_cast<uint64_t*>(mem + o_aggpc);
+        a.agg_pb = reinterpret_cast<uint64_t*>(mem + o_aggpb);
+        a.skey[0] = reinterpret_cast<uint32_t*>(mem + o_skey0);
+        a.skey[1] = reinterpret_cast<uint32_t*>(mem + o_skey1);
+        a.sidx[0] = reinterpret_cast<uint32_t*>(mem + o_sidx0);
+        a.sidx[1] = reinterpret_cast<uint32_t*>(mem + o_sidx1);
+        a.okey = a.skey[passes & 1];
+        a.oidx = a.sidx[passes & 1];
+        a.hist = reinterpret_cast<uint32_t*>(mem + o_hist);
+        a.rcnt = reinterpret_cast<uint32_t*>(mem + o_rcnt);
+        a.written = reinterpret_cast<uint32_t*>(mem + o_written);
+    }
     const bool frames = blocks && grid_s;  // else no echo: the totals are 0
     a.tot_cnt = frames ? a.agg_cnt + (blocks - 1) : nullptr;
     a.tot_bytes = frames ? a.agg_bytes + (blocks - 1) : nullptr;
     a.tot_open = grid_s ? a.agg_co + (grid_s - 1) : nullptr;
 
-    hipLaunchKernelGGL(k_echo_init, dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
-    if (grid_s) hipLaunchKernelGGL(k_echo_conns, dim3(grid_s), dim3(kBlock), 0, s, a);
+    const EcArgs& base = a;  // the kernels the relay does not change take the echo's arguments
+    hipLaunchKernelGGL((k_echo_init<A>), dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
+    if (grid_s) hipLaunchKernelGGL((k_echo_conns<A>), dim3(grid_s), dim3(kBlock), 0, s, a);
     if (frames) {
-        hipLaunchKernelGGL(k_echo_reduce, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(k_echo_reduce, dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, blocks);
-        hipLaunchKernelGGL(k_echo_classify, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(k_echo_classify, dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_d, blocks);
         hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_post, blocks);
-        hipLaunchKernelGGL(k_echo_prefix, dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL(k_echo_size, dim3(blocks), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL(k_echo_prefix, dim3(blocks), dim3(kBlock), 0, s, base);
+        hipLaunchKernelGGL((k_echo_size<A>), dim3(blocks), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cnt, blocks);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_bytes, blocks);
     }
     if (grid_s) {
-        hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, a, 1);
+        hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, base, 1);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_co, grid_s);
     }
-    if (frames) hipLaunchKernelGGL(k_echo_offsets, dim3(blocks), dim3(kBlock), 0, s, a);
+    if constexpr (relay) if (grid_s) {
+        // every connection's frames and bytes, the order, and each connection's base in it
+        if (frames) {
+            a.count_only = 1;
+            hipLaunchKernelGGL((k_echo_offsets<A>), dim3(blocks), dim3(kBlock), 0, s, a);
+            a.count_only = 0;
+        }
+        for (uint32_t pass = 0; pass < passes; ++pass) {
+            const uint32_t shift = 8 * pass;
+            const int from = (int)(pass & 1);
+            engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+                hipLaunchKernelGGL(k_relay_hist, dim3(grid), dim3(kBlock), 0, s, a, tb, shift, from);
+            });
+            engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+                hipLaunchKernelGGL(k_relay_hreduce, dim3(grid), dim3(kBlock), 0, s, a, tb);
+            });
+            hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_h, grid_s);
+            engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+                hipLaunchKernelGGL(k_relay_hscan, dim3(grid), dim3(kBlock), 0, s, a, tb);
+            });
+            engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+                hipLaunchKernelGGL(k_relay_scatter, dim3(grid), dim3(kBlock), 0, s, a, tb, shift, from);
+            });
+        }
+        engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+            hipLaunchKernelGGL(k_relay_oreduce, dim3(grid), dim3(kBlock), 0, s, a, tb);
+        });
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pc, grid_s);
+        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pb, grid_s);
+        engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
+            hipLaunchKernelGGL(k_relay_obase, dim3(grid), dim3(kBlock), 0, s, a, tb);
+        });
+    }
+    if (frames) hipLaunchKernelGGL((k_echo_offsets<A>), dim3(blocks), dim3(kBlock), 0, s, a);
     const uint32_t grid_t = (uint32_t)((E + 1 + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_echo_tail, dim3(grid_t), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL(k_echo_tail, dim3(grid_t), dim3(kBlock), 0, s, base);
+    if constexpr (relay) {
+        engine_grid_chunks(e, ((uint64_t)a.n_rooms + kBlock - 1) / kBlock, [&](uint32_t grid, uint64_t tb) {
+            hipLaunchKernelGGL(k_relay_rooms, dim3(grid), dim3(kBlock), 0, s, a, tb);
+        });
+        engine_grid_chunks(e, ((uint64_t)a.n_receivers + kBlock - 1) / kBlock, [&](uint32_t grid, uint64_t tb) {
+            hipLaunchKernelGGL(k_relay_recv, dim3(grid), dim3(kBlock), 0, s, a, tb);
+        });
+    }
     if (grid_s) {
-        hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, a, 0);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cn, grid_s);
-        hipLaunchKernelGGL(k_echo_finish, dim3(grid_s), dim3(kBlock), 0, s, a);
+        if constexpr (!relay) {
+            hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, base, 0);
+            hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cn, grid_s);
+        }
+        hipLaunchKernelGGL((k_echo_finish<A>), dim3(grid_s), dim3(kBlock), 0, s, a);
         engine_grid_chunks(e, tiles_out + tiles_open, [&](uint32_t grid, uint64_t tb) {
-            hipLaunchKernelGGL(k_echo_emit, dim3(grid), dim3(kBlock), 0, s, a, tb, tiles_out);
+            hipLaunchKernelGGL((k_echo_emit<A>), dim3(grid), dim3(kBlock), 0, s, a, tb, tiles_out);
         });
     }
     return uvws_call_leave(e, prev, what);
@@ -977,4 +1306,61 @@ extern "C" int uvhttp_ws_gpu_echo_messages_inplace(
                             "echo_messages_inplace: n_frames or max_echoes > 2^28 or a bad run_stride");
     if (rc != UVHTTP_WS_GPU_OK) return rc;
     return ec_run(e, a, stream, "echo_messages_inplace launch");
+}
+
+extern "C" int uvhttp_ws_gpu_relay_messages_streams(
+    uvhttp_ws_gpu_engine_t* e, const uint8_t* d_wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+    uint32_t max_frames, const uvhttp_ws_stream_t* d_streams, const uvhttp_ws_stream_result_t* d_results,
+    uint32_t n_streams, const uint8_t* d_enable, const uint32_t* d_room, uint32_t n_rooms, uint32_t flags,
+    const uint8_t* d_carry, uint64_t carry_len, const uint64_t* d_carry_off, uint8_t* d_out, uint64_t out_cap,
+    uint64_t* d_out_off, uint32_t max_frames_out, uvhttp_ws_relay_room_t* d_rooms, const uint32_t* d_recv_room,
+    uint32_t n_receivers, uint32_t* d_sends, uint32_t send_stride, uint8_t* d_open, uint64_t open_cap,
+    uint64_t* d_open_off, uvhttp_ws_echo_conn_t* d_conn, uvhttp_ws_relay_summary_t* d_summary, void* stream) {
+    // k_echo_init / k_echo_finish write the summary's first four fields through the echo's type
+    static_assert(sizeof(uvhttp_ws_relay_summary_t) == 32 && sizeof(uvhttp_ws_relay_room_t) == 32, "ABI");
+    static_assert(offsetof(uvhttp_ws_relay_summary_t, n_frames) == offsetof(uvhttp_ws_echo_summary_t, n_echoes) &&
+                      offsetof(uvhttp_ws_relay_summary_t, status) == offsetof(uvhttp_ws_echo_summary_t, status) &&
+                      offsetof(uvhttp_ws_relay_summary_t, n_bad_rooms) == offsetof(uvhttp_ws_echo_summary_t, reserved) &&
+                      offsetof(uvhttp_ws_relay_summary_t, n_bad_receivers) == offsetof(uvhttp_ws_echo_summary_t, reserved) + 4,
+                  "the relay summary begins as the echo's");
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    if (!d_streams || !d_room || (!d_rooms && n_rooms) || ((!d_recv_room || !d_sends) && n_receivers))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, "relay_messages_streams: NULL argument");
+    if (((uintptr_t)d_room & 3u) || ((uintptr_t)d_rooms & 7u) || ((uintptr_t)d_recv_room & 3u) || ((uintptr_t)d_sends & 3u))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, "relay_messages_streams: misaligned argument");
+    if (n_rooms > (1u << 28) || (d_sends && (send_stride < 8 || (send_stride & 3u))))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, "relay_messages_streams: n_rooms > 2^28 or a bad send_stride");
+    RlArgs a = {};
+    a.wire = d_wire;
+    a.wire_len = wire_len;
+    a.desc = d_desc;
+    a.max_frames = max_frames;
+    a.n_streams = n_streams;
+    a.streams = d_streams;
+    a.results = d_results;
+    a.enable = d_enable;
+    a.flags = flags;
+    a.carry = d_carry;
+    a.carry_len = carry_len;
+    a.carry_off = d_carry_off;
+    a.out = d_out;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    a.max_echoes = max_frames_out;
+    a.open = d_open;
+    a.open_cap = open_cap;
+    a.open_off = d_open_off;
+    a.conn = d_conn;
+    a.sum = reinterpret_cast<uvhttp_ws_echo_summary_t*>(d_summary);
+    a.room = d_room;
+    a.n_rooms = n_rooms;
+    a.rooms = d_rooms;
+    a.recv_room = d_recv_room;
+    a.n_receivers = n_receivers;
+    a.sends = d_sends;
+    a.send_stride = send_stride;
+    const int rc = ec_check(e, a, "relay_messages_streams: NULL argument", "relay_messages_streams: misaligned argument",
+                            "relay_messages_streams: max_frames or max_frames_out > 2^28 or n_streams > 2^31");
+    if (rc != UVHTTP_WS_GPU_OK) return rc;
+    return ec_run(e, a, stream, "relay_messages_streams launch");
 }

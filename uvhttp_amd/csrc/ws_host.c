@@ -942,3 +942,170 @@ int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
     }
     return 0;
 }
+
+/* ---- relay of data messages: the room server's frames of a whole decoded batch -------------- */
+/* The host twin of uvhttp_ws_gpu_relay_messages_streams and the statement of its rules
+ * (include/uvhttp_ws_amd.h): every connection's frames are what uvhttp_ws_echo_messages makes of
+ * it as a server without keys; they are laid out by (room, connection index), every room gets
+ * its run and every receiver its room's. */
+typedef struct {
+    uint32_t key, s;
+} relay_place_t;
+
+static int relay_place_cmp(const void* pa, const void* pb) {
+    const relay_place_t* a = (const relay_place_t*)pa;
+    const relay_place_t* b = (const relay_place_t*)pb;
+    if (a->key != b->key) return a->key < b->key ? -1 : 1;
+    return a->s < b->s ? -1 : a->s > b->s;
+}
+
+/* connection s as the echo twin takes it: its considered frames and its usable carry */
+typedef struct {
+    uint32_t ff, nd;
+    int pending_opcode;
+    uint64_t pending_bytes, carry_len;
+    const uint8_t* carry;
+} relay_conn_t;
+
+static relay_conn_t relay_conn(const uvhttp_ws_stream_t* st, const uvhttp_ws_stream_result_t* q,
+                               uint32_t max_frames, const uint8_t* carry,
+                               uint64_t carry_len, const uint64_t* carry_off, uint32_t s) {
+    relay_conn_t c;
+    c.ff = q->first_frame;
+    c.nd = q->n_delivered;
+    if (q->first_status == UVHTTP_WS_FRAME_ERR_CAPACITY || q->first_status == UVHTTP_WS_FRAME_ERR_LAYOUT ||
+        q->first_status == UVHTTP_WS_FRAME_ERR_DEVICE)
+        c.nd = 0;
+    if (c.ff >= max_frames) c.nd = 0;
+    else if (c.nd > max_frames - c.ff) c.nd = max_frames - c.ff;
+    if (c.nd == 0) c.ff = 0;
+    c.pending_opcode = st->pending_opcode;
+    c.pending_bytes = st->pending_bytes;
+    c.carry = NULL;
+    c.carry_len = 0; /* unusable: the echo twin says NO_CARRY when pending_bytes != 0 */
+    if (c.pending_bytes != 0 && carry != NULL && carry_off != NULL) {
+        const uint64_t lo = carry_off[s], hi = carry_off[s + 1];
+        if (hi >= lo && hi <= carry_len && hi - lo == c.pending_bytes) {
+            c.carry = carry + lo;
+            c.carry_len = c.pending_bytes;
+        }
+    }
+    return c;
+}
+
+int uvhttp_ws_relay_messages(const uint8_t* wire, uint64_t wire_len,
+                             const uvhttp_ws_frame_desc_t* desc, uint32_t max_frames,
+                             const uvhttp_ws_stream_t* streams,
+                             const uvhttp_ws_stream_result_t* results, uint32_t n_streams,
+                             const uint8_t* enable, const uint32_t* room, uint32_t n_rooms,
+                             uint32_t flags, const uint8_t* carry, uint64_t carry_len,
+                             const uint64_t* carry_off, uint8_t* out, uint64_t out_cap,
+                             uint64_t* out_off, uint32_t max_frames_out,
+                             uvhttp_ws_relay_room_t* rooms, const uint32_t* recv_room,
+                             uint32_t n_receivers, uint32_t* sends, uint32_t send_stride,
+                             uint8_t* open, uint64_t open_cap, uint64_t* open_off,
+                             uvhttp_ws_echo_conn_t* conn, uvhttp_ws_relay_summary_t* summary) {
+    if (streams == NULL || results == NULL || room == NULL || out_off == NULL || open_off == NULL ||
+        conn == NULL || summary == NULL || (desc == NULL && max_frames != 0) ||
+        (wire == NULL && wire_len != 0) || (out == NULL && out_cap != 0) || (rooms == NULL && n_rooms != 0) ||
+        ((recv_room == NULL || sends == NULL) && n_receivers != 0) ||
+        (sends != NULL && (send_stride < 8 || (send_stride & 3u))))
+        return -1;
+    memset(summary, 0, sizeof(*summary));
+    relay_place_t* order = (relay_place_t*)malloc(((size_t)n_streams + 1) * sizeof(*order));
+    if (order == NULL) return -1;
+    /* sizes: every connection through the echo twin with no room for anything */
+    uint64_t n_total = 0, bytes_total = 0, open_total = 0, dummy_off[1];
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        const int en = enable == NULL || enable[s] != 0;
+        const relay_conn_t c = relay_conn(&streams[s], &results[s], max_frames, carry, carry_len, carry_off, s);
+        uvhttp_ws_echo_conn_t* r = &conn[s];
+        memset(r, 0, sizeof(*r));
+        order[s].key = room[s] < n_rooms ? room[s] : n_rooms;
+        order[s].s = s;
+        if (!en) continue;
+        if (c.pending_bytes != 0 && c.carry_len != c.pending_bytes) {
+            r->status = UVHTTP_WS_ECHO_NO_CARRY;
+        } else if (room[s] >= n_rooms) {
+            r->status = UVHTTP_WS_RELAY_BAD_ROOM;
+            summary->n_bad_rooms++;
+        } else {
+            (void)uvhttp_ws_echo_messages(wire, wire_len, desc, c.ff, c.nd, 1, 1, NULL, flags, c.pending_opcode,
+                                          c.pending_bytes, c.carry, c.carry_len, NULL, 0, dummy_off, 0, NULL, 0, r);
+            if (r->status == UVHTTP_WS_ECHO_ERR_CAPACITY) r->status = UVHTTP_WS_ECHO_OK; /* sized only */
+        }
+        n_total += r->n_echoes;
+        bytes_total += r->out_len;
+        open_total += r->open_len;
+    }
+    for (uint32_t k = 0; k < n_receivers; ++k)
+        if (recv_room[k] >= n_rooms) summary->n_bad_receivers++;
+    summary->out_bytes = bytes_total;
+    summary->open_bytes = open_total;
+    summary->n_frames = (uint32_t)n_total;
+    const int fits = n_total <= max_frames_out && bytes_total <= out_cap && (open == NULL || open_total <= open_cap);
+    summary->status = fits ? UVHTTP_WS_ECHO_OK : UVHTTP_WS_ECHO_ERR_CAPACITY;
+    for (uint64_t j = 0; j <= max_frames_out; ++j) out_off[j] = fits ? bytes_total : 0;
+    for (uint32_t r = 0; r < n_rooms; ++r) memset(&rooms[r], 0, sizeof(rooms[r]));
+    if (!fits) {
+        for (uint32_t s = 0; s <= n_streams; ++s) open_off[s] = 0;
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            memset(&conn[s], 0, sizeof(conn[s]));
+            conn[s].status = UVHTTP_WS_ECHO_ERR_CAPACITY;
+        }
+    } else {
+        /* the open messages' places: connection index order */
+        uint64_t at_open = 0;
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            open_off[s] = at_open;
+            at_open += conn[s].open_len;
+        }
+        open_off[n_streams] = at_open;
+        /* the frames: (room, connection index) order */
+        qsort(order, n_streams, sizeof(*order), relay_place_cmp);
+        order[n_streams].key = 0xFFFFFFFFu;
+        uint64_t j = 0, at = 0;
+        uint32_t p = 0;
+        for (uint32_t r = 0; r <= n_rooms; ++r) { /* r == n_rooms: the connections after every room */
+            if (r < n_rooms) {
+                rooms[r].first_frame = (uint32_t)j;
+                rooms[r].out_off = at;
+            }
+            for (; p < n_streams && order[p].key == r; ++p) {
+                const uint32_t s = order[p].s;
+                uvhttp_ws_echo_conn_t* q = &conn[s];
+                const uint32_t n = q->n_echoes;
+                q->first_echo = (uint32_t)j;
+                if (q->status != UVHTTP_WS_ECHO_OK || (enable != NULL && enable[s] == 0)) continue;
+                const relay_conn_t c = relay_conn(&streams[s], &results[s], max_frames, carry, carry_len, carry_off, s);
+                uint64_t* off = (uint64_t*)malloc(((size_t)n + 1) * sizeof(*off));
+                if (off == NULL) {
+                    free(order);
+                    return -1;
+                }
+                uvhttp_ws_echo_conn_t again;
+                (void)uvhttp_ws_echo_messages(wire, wire_len, desc, c.ff, c.nd, 1, 1, NULL, flags, c.pending_opcode,
+                                              c.pending_bytes, c.carry, c.carry_len, out != NULL ? out + at : NULL,
+                                              q->out_len, off, n, open != NULL ? open + open_off[s] : NULL,
+                                              q->open_len, &again);
+                q->open_opcode = again.open_opcode;
+                for (uint32_t k = 0; k < n; ++k) out_off[j + k] = at + off[k];
+                free(off);
+                j += n;
+                at += q->out_len;
+            }
+            if (r < n_rooms) {
+                rooms[r].n_frames = (uint32_t)j - rooms[r].first_frame;
+                rooms[r].out_len = at - rooms[r].out_off;
+            }
+        }
+    }
+    for (uint32_t k = 0; k < n_receivers; ++k) {
+        uint32_t* run = (uint32_t*)((char*)sends + (size_t)k * send_stride);
+        const int ok = recv_room[k] < n_rooms;
+        run[0] = ok ? rooms[recv_room[k]].first_frame : 0;
+        run[1] = ok ? rooms[recv_room[k]].n_frames : 0;
+    }
+    free(order);
+    return 0;
+}
