@@ -304,6 +304,57 @@ int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* eng, const uint8_t* fram
                                uvhttp_tls_send_summary_t* summary, uint8_t* out, uint64_t out_cap,
                                void* stream);
 
+/* Seal several parts per send: one numbered, contiguous send per connection out of the frames
+ * several builders left (uvhttp_ws_gpu_echo_messages_streams or _relay_, _control_replies_,
+ * _close_frames_streams), each with its own frame table and its own per-connection run.  No frame
+ * byte is copied: `frames` is ONE device buffer, the send arena, and the caller hands sub-ranges
+ * of it to the builders as their d_out; part p says where its builder wrote (base, len = that
+ * builder's out_cap), where its offsets lie (frame_off: n_frames + 1 entries relative to base, a
+ * builder's d_out_off as it lies) and where send s's run (first_frame, n_frames: two uint32_t)
+ * lies, at (char*)runs + s * run_stride — the builders' d_runs / run_stride convention.  The part
+ * table itself is host memory, passed by value; the pointers inside are device pointers.
+ *
+ * Semantics.  Send s is the frame sequence part 0's run, then part 1's run, ...  sends[s] supplies
+ * seq, key and type; its first_frame / n_frames are ignored.  Everything else is seal_frames':
+ * every frame is cut on its own into ceil(F / max_fragment) records, a record never holds bytes of
+ * two frames (and so never of two parts), an empty frame gives no record, the records are numbered
+ * seq, seq + 1, ... across all parts and lie back to back in out, sends in index order; results
+ * and summary are seal_frames' structs with plain_len the sum over the parts; records[r].src_off
+ * = base_p + frame_off_p[f] + cut, so records[] is a valid uvhttp_tls_gpu_seal_records input with
+ * src = frames.  Parts may overlap and the same table may be listed twice with two run tables: a
+ * relay without the sender is the relay's table once with the frames before the sender's own and
+ * once with those after.
+ *
+ * Per-send failures, in seal_frames' order: ERR_KEY as there; ERR_RANGE if any part's run has
+ * first_frame + n_frames > that part's n_frames, or a frame of the run has decreasing offsets or
+ * frame_off[f + 1] > len.  A failed send has 0 records and next_seq = seq; the others are not
+ * affected, and a bad frame outside every run harms nobody.  Capacity: exactly seal_frames' rule.
+ *
+ * EINVAL: n_parts 0 or above UVHTTP_TLS_MAX_PARTS; a part with base + len > frames_len, a null
+ * or misaligned frame_off (8) or runs (4), run_stride < 8 or not a multiple of 4; the null
+ * pointers seal_frames refuses; max_fragment > 16384; more than 2^26 sends, 2^28 frames over all
+ * parts or 2^28 records.  n_sends = 0 returns OK with a zeroed summary.  Asynchronous on `stream`,
+ * no host synchronisation, scratch in the engine (12 bytes per frame table entry, 44 per send):
+ * graph-capturable after one uncaptured call of the same or a larger shape. */
+#define UVHTTP_TLS_MAX_PARTS 8
+typedef struct {
+    uint64_t base;             /* the part's frames start at frames + base */
+    uint64_t len;              /* bytes its builder was given (its out_cap); base + len <= frames_len */
+    const uint64_t* frame_off; /* n_frames + 1 offsets relative to base, as d_out_off lies */
+    const uint32_t* runs;      /* send s: (first_frame, n_frames) at (char*)runs + s * run_stride */
+    uint32_t run_stride;       /* >= 8, a multiple of 4 */
+    uint32_t n_frames;         /* entries of the table (max_replies, max_echoes, ...) */
+} uvhttp_tls_part_t;
+
+int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* eng, const uint8_t* frames,
+                              uint64_t frames_len, const uvhttp_tls_part_t* parts, uint32_t n_parts,
+                              const uvhttp_tls_send_t* sends, uint32_t n_sends,
+                              const uvhttp_tls_key_t* keys, uint32_t n_keys, uint32_t max_fragment,
+                              uvhttp_tls_seal_t* records, uint32_t max_records,
+                              uvhttp_tls_send_result_t* results,
+                              uvhttp_tls_send_summary_t* summary, uint8_t* out, uint64_t out_cap,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

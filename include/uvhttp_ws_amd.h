@@ -1109,6 +1109,91 @@ int uvhttp_ws_relay_messages(const uint8_t* wire, uint64_t wire_len,
                              uint8_t* open, uint64_t open_cap, uint64_t* open_off,
                              uvhttp_ws_echo_conn_t* conn, uvhttp_ws_relay_summary_t* summary);
 
+/* ---- the server's own CLOSE frames: 1002 after a failed decode, 1007 after invalid UTF-8 ---- */
+/* When a process_data call fails, on_websocket_read closes the WebSocket itself:
+ * uvhttp_ws_close(NULL, ws_conn, 1002, "protocol error") (src/uvhttp_connection.c:1166-1174,
+ * src/uvhttp_websocket.c:627-666), one CLOSE frame built by uvhttp_ws_build_frame(opcode 8, mask =
+ * !is_server, fin 1).  This pass builds those frames for a whole decoded batch, and the 1007
+ * close the UTF-8 verdicts exist for (RFC 6455 §7.4.1, §8.1), in the layout of the control
+ * replies, so they are one more part of the batch's send (uvhttp_tls_gpu_seal_parts) and a CLOSE
+ * is the last frame of its connection's send by construction.  One lane per connection; no
+ * descriptor and no wire byte is read.
+ *
+ * Rule, per connection s.  No frame if d_enable is given and d_enable[s] == 0; if
+ * d_results[s].first_status is ERR_CAPACITY, ERR_LAYOUT or ERR_DEVICE (the call failed, not the
+ * peer); or if d_reply_conn is given and d_reply_conn[s].closed is set (the reference's send_frame
+ * refuses once the state has left OPEN, and the CLOSE echo already closes the connection).
+ * Otherwise, if d_verdict is given and d_verdict[s].status is UVHTTP_WS_UTF8_INVALID: code 1007
+ * with an empty reason — this project's choice, the reference never checks; it wins over a decode
+ * failure, because first_invalid is a delivered frame and so precedes the failing one.  Otherwise,
+ * if first_status < 0: code 1002 with the reason "protocol error", byte for byte the reference's
+ * frame.  Everything else (BAD_RANGE included: a caller error) gives no frame.  A client stream
+ * (is_server == 0) masks its frame with d_mask_keys[s] (k0 = low byte); when d_mask_keys is NULL
+ * it gets no frame and status UVHTTP_WS_CLOSE_NO_KEYS.
+ *
+ * Layout.  Frames lie back to back in d_out in connection order; d_out_off has n_streams + 1
+ * entries, d_out_off[j] the start of frame j and every entry from the frame count on the total:
+ * a valid frame table with n_frames = n_streams.  Connection s's run (closes of the connections
+ * before it, then 0 or 1) goes to (char*)d_runs + s * run_stride (d_runs may be NULL).
+ *
+ * d_clear_runs (a host array of n_clear <= 4 device pointers, strides clear_stride[k]): for a
+ * connection that gets the 1007 close the pass writes n_frames = 0 into the second word of its
+ * run in each of those tables.  Pass the connection's echo and reply runs and it is failed per RFC
+ * 6455 §7.1.7 with nothing but the close.  Stream order: the pass must run after the passes that
+ * write those tables, and before the seal that reads them.
+ *
+ * Capacity, the replies' rule: if the bytes exceed out_cap nothing is written to d_out, every
+ * d_out_off entry and run is 0, no run is cleared, every per-connection result is zero but for
+ * status ERR_CAPACITY, and the summary holds the totals needed with status ERR_CAPACITY.
+ *
+ * Device pointers: d_streams, d_results, d_out_off and d_summary 8-byte aligned, the others 4
+ * (d_out, d_enable 1).  EINVAL for NULL (d_verdict, d_reply_conn, d_enable, d_mask_keys, d_runs
+ * and d_clear_runs excepted) or misaligned arguments, a run or clear stride < 8 or not a multiple
+ * of 4, n_clear > 4, flags != 0, n_streams > 2^31.  Asynchronous on `stream` under the engine's
+ * stream rule; 16 bytes of engine scratch per 256 connections, grown on demand: graph-capturable
+ * once one uncaptured call of the same or a larger n_streams has been made. */
+#define UVHTTP_WS_CLOSE_OK 0
+#define UVHTTP_WS_CLOSE_ERR_CAPACITY 1  /* the whole call: out_cap too small */
+#define UVHTTP_WS_CLOSE_NO_KEYS 3       /* a client connection to close and d_mask_keys == NULL */
+#define UVHTTP_WS_CLOSE_MAX_CLEAR 4
+
+typedef struct {            /* 16 B, one per connection, device-written */
+    uint32_t code;          /* 1002, 1007, or 0: no frame */
+    uint32_t out_len;       /* bytes of its frame */
+    uint8_t status;         /* UVHTTP_WS_CLOSE_* */
+    uint8_t reserved[7];
+} uvhttp_ws_close_conn_t;
+
+typedef struct {            /* 32 B */
+    uint64_t out_bytes;     /* bytes of d_out the call needs */
+    uint32_t n_closes;      /* n_1002 + n_1007 */
+    uint32_t n_1002;
+    uint32_t n_1007;
+    int32_t status;         /* UVHTTP_WS_CLOSE_OK or UVHTTP_WS_CLOSE_ERR_CAPACITY */
+    uint32_t reserved[2];
+} uvhttp_ws_close_summary_t;
+
+int uvhttp_ws_gpu_close_frames_streams(uvhttp_ws_gpu_engine_t* eng, const uvhttp_ws_stream_t* d_streams,
+                                       const uvhttp_ws_stream_result_t* d_results, uint32_t n_streams,
+                                       const uvhttp_ws_utf8_conn_verdict_t* d_verdict,
+                                       const uvhttp_ws_reply_conn_t* d_reply_conn,
+                                       const uint8_t* d_enable, const uint32_t* d_mask_keys,
+                                       uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                                       uint64_t* d_out_off, uint32_t* d_runs, uint32_t run_stride,
+                                       uint32_t* const* d_clear_runs, const uint32_t* clear_stride,
+                                       uint32_t n_clear, uvhttp_ws_close_conn_t* d_conn,
+                                       uvhttp_ws_close_summary_t* d_summary, void* stream);
+/* Host twin (plain C, host copies of the same tables): all connections of the call at once and
+ * the same outputs, byte for byte; the statement of the rule.  Returns 0, or -1 for an argument
+ * the device call answers with EINVAL. */
+int uvhttp_ws_close_frames(const uvhttp_ws_stream_t* streams, const uvhttp_ws_stream_result_t* results,
+                           uint32_t n_streams, const uvhttp_ws_utf8_conn_verdict_t* verdict,
+                           const uvhttp_ws_reply_conn_t* reply_conn, const uint8_t* enable,
+                           const uint32_t* mask_keys, uint32_t flags, uint8_t* out, uint64_t out_cap,
+                           uint64_t* out_off, uint32_t* runs, uint32_t run_stride,
+                           uint32_t* const* clear_runs, const uint32_t* clear_stride, uint32_t n_clear,
+                           uvhttp_ws_close_conn_t* conn, uvhttp_ws_close_summary_t* summary);
+
 /* ---- host-memory pipeline (libuv read buffers in, decoded payloads out) ---------------- */
 /* A pipeline owns `depth` slots.  Each slot = a pinned host staging buffer (the caller
  * writes masked frames there, e.g. hands it out from the libuv alloc callback) and a device

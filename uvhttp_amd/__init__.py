@@ -138,6 +138,38 @@ class ReplySummary(C.Structure):
         return {k: getattr(self, k) for k in ("out_bytes", "n_replies", "n_closed_conns", "status")}
 
 
+CLOSE_OK, CLOSE_ERR_CAPACITY, CLOSE_NO_KEYS = 0, 1, 3  # UVHTTP_WS_CLOSE_*
+CLOSE_MAX_CLEAR = 4
+
+
+class CloseConn(C.Structure):
+    """uvhttp_ws_close_conn_t (16 B)."""
+    _fields_ = [("code", C.c_uint32), ("out_len", C.c_uint32), ("status", C.c_uint8),
+                ("reserved", C.c_uint8 * 7)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("code", "out_len", "status")}
+
+
+class CloseSummary(C.Structure):
+    """uvhttp_ws_close_summary_t (32 B)."""
+    _fields_ = [("out_bytes", C.c_uint64), ("n_closes", C.c_uint32), ("n_1002", C.c_uint32),
+                ("n_1007", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("out_bytes", "n_closes", "n_1002", "n_1007", "status")}
+
+
+TLS_MAX_PARTS = 8  # UVHTTP_TLS_MAX_PARTS
+
+
+class TlsPart(C.Structure):
+    """uvhttp_tls_part_t (40 B): one part of a uvhttp_tls_gpu_seal_parts send.  Host memory; frame_off
+    and runs are device addresses."""
+    _fields_ = [("base", C.c_uint64), ("len", C.c_uint64), ("frame_off", C.c_void_p),
+                ("runs", C.c_void_p), ("run_stride", C.c_uint32), ("n_frames", C.c_uint32)]
+
+
 ECHO_SERVER_SEND = 0x1  # UVHTTP_WS_ECHO_SERVER_SEND
 ECHO_OK, ECHO_ERR_CAPACITY, ECHO_BAD_RANGE, ECHO_NO_KEYS, ECHO_NO_CARRY = range(5)
 
@@ -433,6 +465,10 @@ def load_library(path: str) -> C.CDLL:
                                                            u32, vp, u64, vp, vp, vp, vp]),
         "uvhttp_ws_relay_messages": (C.c_int, [vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u32, vp, u64, vp,
                                                vp, u64, vp, u32, vp, vp, u32, vp, u32, vp, u64, vp, vp, vp]),
+        "uvhttp_ws_gpu_close_frames_streams": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, u64, vp,
+                                                         vp, u32, vp, vp, u32, vp, vp, vp]),
+        "uvhttp_ws_close_frames": (C.c_int, [vp, vp, u32, vp, vp, vp, vp, u32, vp, u64, vp, vp, u32, vp,
+                                             vp, u32, vp, vp]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -515,6 +551,8 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_tls_gpu_seal_records": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, u64, vp]),
         "uvhttp_tls_gpu_seal_frames": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, u32, u32, vp,
                                                  u32, vp, vp, vp, u64, vp]),
+        "uvhttp_tls_gpu_seal_parts": (C.c_int, [vp, vp, u64, C.POINTER(TlsPart), u32, vp, u32, vp, u32,
+                                                u32, vp, u32, vp, vp, vp, u64, vp]),
         "uvhttp_tls_gpu_ws_streams": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
@@ -641,6 +679,36 @@ def control_replies(wire, desc, first_frame, n_delivered, is_server=1, enable=1,
         raise ValueError("uvhttp_ws_control_replies: bad argument")
     ok = res.status != REPLY_ERR_CAPACITY
     return bytes(out)[: res.out_len if ok else 0], list(off), res.as_dict()
+
+
+def close_frames(streams, results, n_streams, verdict=None, reply_conn=None, enable=None,
+                 mask_keys=None, flags=0, out_cap=None, run_stride=8, clear_runs=(), clear_stride=()):
+    """uvhttp_ws_close_frames: the host twin of GpuEngine.close_frames_streams.  streams / results
+    / verdict / reply_conn = numpy arrays holding the C structs (any dtype, contiguous), enable =
+    uint8[n_streams] or None, mask_keys = uint32[n_streams] or None, clear_runs = writable numpy
+    uint8 / uint32 arrays whose runs of 1007 connections get n_frames = 0 (in place).  out_cap
+    None = enough for every connection.  Returns (frame bytes, out_off [n_streams + 1], runs
+    uint32 [n_streams, run_stride // 4], [CloseConn.as_dict()], CloseSummary.as_dict())."""
+    import numpy as np
+    if out_cap is None:
+        out_cap = 22 * n_streams
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    out = np.zeros(max(1, out_cap), dtype=np.uint8)
+    out_off = np.zeros(n_streams + 1, dtype=np.uint64)
+    runs = np.zeros((max(1, n_streams), max(2, run_stride // 4)), dtype=np.uint32)
+    conn = (CloseConn * max(1, n_streams))()
+    summ = CloseSummary()
+    n_clear = len(clear_runs)
+    cp = (C.c_void_p * max(1, n_clear))(*[a.ctypes.data for a in clear_runs])
+    cs = (C.c_uint32 * max(1, n_clear))(*clear_stride)
+    rc = lib().uvhttp_ws_close_frames(ptr(streams), ptr(results), n_streams, ptr(verdict), ptr(reply_conn),
+                                      ptr(enable), ptr(mask_keys), flags, ptr(out), out_cap, ptr(out_off),
+                                      ptr(runs), run_stride, cp, cs, n_clear, conn, C.byref(summ))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_close_frames: bad argument")
+    sd = summ.as_dict()
+    n = int(out_off[n_streams])
+    return out[:n].tobytes(), out_off, runs, [conn[k].as_dict() for k in range(n_streams)], sd
 
 
 def echo_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, mask_keys=None,
@@ -1140,6 +1208,49 @@ class GpuEngine:
             "control_replies_inplace")
         return out, out_off, conn, summary
 
+    def close_frames_streams(self, streams_dev, results, n_streams, out_cap, verdict=None,
+                             reply_conn=None, enable=None, mask_keys=None, flags=0, out=None,
+                             out_off=None, runs=None, run_stride=8, clear_runs=(), clear_stride=(),
+                             conn=None, summary=None, stream=None):
+        """uvhttp_ws_gpu_close_frames_streams after a stream decode (and, for the optional inputs,
+        validate_utf8_streams -> verdict, control_replies_streams -> reply_conn): the server's own
+        1002 / 1007 CLOSE frames.  mask_keys = device int32[n_streams] or None; clear_runs = device
+        tensors (or views into send tables at first_frame) whose runs a 1007 close empties, with
+        their strides.  Returns (out, out_off, conn, summary) device tensors: the frames,
+        n_streams + 1 int64 offsets, n_streams 16-byte uvhttp_ws_close_conn_t and the 32-byte
+        uvhttp_ws_close_summary_t."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = t.zeros(max(16, out_cap), dtype=t.uint8, device=dev)
+        if out_off is None:
+            out_off = t.zeros(n_streams + 1, dtype=t.int64, device=dev)
+        if conn is None:
+            conn = t.zeros(max(1, n_streams) * C.sizeof(CloseConn), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(CloseSummary), dtype=t.uint8, device=dev)
+        n_clear = len(clear_runs)
+        cp = (C.c_void_p * max(1, n_clear))(*[x.data_ptr() for x in clear_runs])
+        cs = (C.c_uint32 * max(1, n_clear))(*clear_stride)
+        self._check(self._L.uvhttp_ws_gpu_close_frames_streams(
+            self.h, self._ptr(streams_dev), self._ptr(results), n_streams, self._ptr(verdict),
+            self._ptr(reply_conn), self._ptr(enable), self._ptr(mask_keys), flags, self._ptr(out), out_cap,
+            self._ptr(out_off), self._ptr(runs), run_stride, cp, cs, n_clear, self._ptr(conn),
+            self._ptr(summary), self._stream(stream)), "close_frames_streams")
+        return out, out_off, conn, summary
+
+    @staticmethod
+    def read_close_conns(conn, n):
+        """host copy of the first n per-connection close results -> [dict] (CloseConn.as_dict)"""
+        sz = C.sizeof(CloseConn)
+        raw = conn[: n * sz].cpu().numpy().tobytes()
+        return [CloseConn.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_close_summary(summary) -> dict:
+        raw = summary[: C.sizeof(CloseSummary)].cpu().numpy().tobytes()
+        return CloseSummary.from_buffer_copy(raw).as_dict()
+
     def _echo_out(self, n_streams, max_echoes, out_cap, out, out_off, open_off, conn, summary):
         t = self.torch
         dev = f"cuda:{self.device}"
@@ -1515,6 +1626,37 @@ class TlsEngine:
             C.c_void_p(keys.data_ptr()), n_keys, max_fragment, C.c_void_p(records.data_ptr()),
             max_records, C.c_void_p(results.data_ptr()), C.c_void_p(summary.data_ptr()),
             C.c_void_p(out.data_ptr()), out.numel(), self._stream(stream)), "seal_frames")
+        return records, results, summary
+
+
+    def seal_parts(self, frames, parts, sends, n_sends, keys, n_keys, max_records, out,
+                   max_fragment=0, records=None, results=None, summary=None, frames_len=None,
+                   stream=None):
+        """uvhttp_tls_gpu_seal_parts: frames = the send arena (device uint8), parts = a sequence of
+        TlsPart or of (base, len, frame_off tensor, runs tensor, run_stride, n_frames) tuples, sends
+        a device tensor of uvhttp_tls_send_t (seq, key, type) -> (records, results, summary) device
+        tensors, as seal_frames."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if records is None:
+            records = t.zeros(max(1, max_records) * TLS_SEAL_BYTES, dtype=t.uint8, device=dev)
+        if results is None:
+            results = t.zeros(max(1, n_sends) * TLS_SEND_RESULT_BYTES, dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(TLS_SEND_SUMMARY_BYTES, dtype=t.uint8, device=dev)
+        tab = (TlsPart * max(1, len(parts)))()
+        for k, p in enumerate(parts):
+            if isinstance(p, TlsPart):
+                tab[k] = p
+            else:
+                base, ln, off, runs, stride, n = p
+                tab[k] = TlsPart(base, ln, off.data_ptr() if hasattr(off, "data_ptr") else off,
+                                 runs.data_ptr() if hasattr(runs, "data_ptr") else runs, stride, n)
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        self._check(self._L.uvhttp_tls_gpu_seal_parts(
+            self.h, ptr(frames), frames.numel() if frames_len is None else frames_len, tab, len(parts),
+            ptr(sends), n_sends, ptr(keys), n_keys, max_fragment, ptr(records), max_records,
+            ptr(results), ptr(summary), ptr(out), out.numel(), self._stream(stream)), "seal_parts")
         return records, results, summary
 
 

@@ -2451,6 +2451,197 @@ __global__ __launch_bounds__(kBlock) void k_tls_send_fill(SendArgs a) {
     }
 }
 
+// ---- send side, several parts per send (uvhttp_tls_gpu_seal_parts) ----------------------------
+//
+// A part is a frame table of its own plus a per-send run, all inside one frames buffer.  The plan
+// is the one above with the frame scan done per part: part p's scan lies at fr_rec / fr_bad
+// [fbase[p], fbase[p] + n_frames_p], its workgroups are blocks [bbase[p], bbase[p + 1]) of one
+// launch.  A send's records, bytes and status are sums over its parts' runs; the scan over the
+// sends and its results are k_tls_send_scan / k_tls_send_write as they stand (they read only
+// sends[].seq, sw, sblk and n_total).  The fill finds a record's send, then walks the at most 8
+// parts by their record counts, then searches the frame in that part's scan.
+
+struct PartsArgs {
+    uvhttp_tls_part_t part[UVHTTP_TLS_MAX_PARTS];
+    uint32_t fbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's entries in fr_rec / fr_bad
+    uint32_t bbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's workgroups in the frame launches
+    uint32_t n_parts;
+    uint32_t max_fragment;
+    const uvhttp_tls_send_t* sends;
+    uint32_t n_sends;
+    uint32_t n_keys;
+    const KeySched* sched;
+    uvhttp_tls_seal_t* records;
+    uint32_t max_records;
+    uint64_t* fr_rec;
+    uint32_t* fr_bad;
+    uint64_t* fblk;       // per workgroup of the frame launches: [2b] records, [2b+1] bad frames
+    SendWork* sw;
+    uint64_t* sblk;
+    const uint32_t* s_first;
+    const uint64_t* s_out;
+    const uint32_t* n_total;
+};
+
+// the part a workgroup of the frame launches works on
+__device__ inline uint32_t parts_of_block(const PartsArgs& a, uint32_t b) {
+    uint32_t p = 0;
+    while (p + 1 < a.n_parts && b >= a.bbase[p + 1]) ++p;
+    return p;
+}
+
+// frame i of part p: its records and whether it is bad (offsets decrease, or reach past len)
+__device__ inline void parts_frame(const PartsArgs& a, uint32_t p, uint32_t i, uint64_t* rec, uint64_t* bad) {
+    *rec = 0;
+    *bad = 0;
+    const uvhttp_tls_part_t& q = a.part[p];
+    if (i >= q.n_frames) return;
+    const uint64_t b = q.frame_off[i], e = q.frame_off[i + 1];
+    if (b > e || e > q.len) {
+        *bad = 1;
+        return;
+    }
+    *rec = (e - b + a.max_fragment - 1) / a.max_fragment;
+}
+
+__device__ inline void parts_run(const uvhttp_tls_part_t& q, uint32_t s, uint32_t* first, uint32_t* n) {
+    const uint32_t* r = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(q.runs) +
+                                                          (uint64_t)s * q.run_stride);
+    *first = r[0];
+    *n = r[1];
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_parts_frame_count(PartsArgs a) {
+    const uint32_t p = parts_of_block(a, blockIdx.x);
+    uint64_t rec, bad, tr, tb;
+    parts_frame(a, p, (blockIdx.x - a.bbase[p]) * kBlock + threadIdx.x, &rec, &bad);
+    (void)block_exclusive_sum<uint64_t>(rec, &tr);
+    (void)block_exclusive_sum<uint64_t>(bad, &tb);
+    if (threadIdx.x == 0) {
+        a.fblk[2 * blockIdx.x] = tr;
+        a.fblk[2 * blockIdx.x + 1] = tb;
+    }
+}
+
+// one workgroup per part: the exclusive prefix of its workgroups' sums
+__global__ __launch_bounds__(kBlock) void k_tls_parts_frame_scan(PartsArgs a) {
+    uint64_t t[2];
+    const uint32_t p = blockIdx.x;
+    scan_block_sums<2>(a.fblk + 2 * (uint64_t)a.bbase[p], a.bbase[p + 1] - a.bbase[p], t);
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_parts_frame_write(PartsArgs a) {
+    const uint32_t p = parts_of_block(a, blockIdx.x);
+    const uint32_t i = (blockIdx.x - a.bbase[p]) * kBlock + threadIdx.x;
+    uint64_t rec, bad, tr, tb;
+    parts_frame(a, p, i, &rec, &bad);
+    const uint64_t pr = a.fblk[2 * blockIdx.x] + block_exclusive_sum<uint64_t>(rec, &tr);
+    const uint64_t pb = a.fblk[2 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(bad, &tb);
+    if (i <= a.part[p].n_frames) {
+        a.fr_rec[(uint64_t)a.fbase[p] + i] = pr;
+        a.fr_bad[(uint64_t)a.fbase[p] + i] = (uint32_t)pb;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_parts_count(PartsArgs a) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    uint64_t n_rec = 0, bytes = 0, failed = 0;
+    if (s < a.n_sends) {
+        const uvhttp_tls_send_t sd = a.sends[s];
+        int32_t st = 0;
+        uint32_t over = 0;
+        if (sd.key >= a.n_keys || sd.key > 0xFFFFu || a.sched[sd.key].nr == 0) {
+            st = UVHTTP_TLS_REC_ERR_KEY;
+        } else {
+            uint64_t plain = 0;
+            for (uint32_t p = 0; p < a.n_parts; ++p) {
+                const uvhttp_tls_part_t& q = a.part[p];
+                uint32_t first, n;
+                parts_run(q, s, &first, &n);
+                const uint64_t last = (uint64_t)first + n;
+                const uint64_t fb = a.fbase[p];
+                if (last > q.n_frames || a.fr_bad[fb + last] != a.fr_bad[fb + first]) {
+                    st = UVHTTP_TLS_REC_ERR_RANGE;
+                    break;
+                }
+                n_rec += a.fr_rec[fb + last] - a.fr_rec[fb + first];
+                // (no bad frame in the run: its offsets do not decrease)
+                if (n) plain += q.frame_off[last] - q.frame_off[first];
+            }
+            if (st) {
+                n_rec = 0;
+            } else {
+                const KeySched* k = a.sched + sd.key;
+                over = 5 + 16 + explicit_len(k->version, k->cipher) +
+                       (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
+                bytes = plain + n_rec * over;
+            }
+        }
+        failed = st ? 1 : 0;
+        a.sw[s] = SendWork{n_rec, bytes, st, over};
+    }
+    uint64_t tn, tb, tf;
+    (void)block_exclusive_sum<uint64_t>(n_rec, &tn);
+    (void)block_exclusive_sum<uint64_t>(bytes, &tb);
+    (void)block_exclusive_sum<uint64_t>(failed, &tf);
+    if (threadIdx.x == 0) {
+        a.sblk[3 * blockIdx.x] = tn;
+        a.sblk[3 * blockIdx.x + 1] = tb;
+        a.sblk[3 * blockIdx.x + 2] = tf;
+    }
+}
+
+// one lane per record: its send (the last one whose first_record <= r), its part (the first one
+// whose records, added to those of the parts before it, pass the record's place in the send), its
+// frame (the last one of the part's run whose record prefix <= the place in the part's scan)
+__global__ __launch_bounds__(kBlock) void k_tls_parts_fill(PartsArgs a) {
+    const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
+    for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
+        uint32_t lo = 0, hi = a.n_sends;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.s_first[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t s = lo;
+        const uvhttp_tls_send_t sd = a.sends[s];
+        const uint64_t k = r - a.s_first[s];
+        uint64_t before = 0, plain = 0;  // records and frame bytes of the parts before the record's
+        for (uint32_t p = 0; p < a.n_parts; ++p) {
+            const uvhttp_tls_part_t& q = a.part[p];
+            uint32_t first, cnt;
+            parts_run(q, s, &first, &cnt);
+            const uint64_t* fr = a.fr_rec + a.fbase[p];
+            const uint64_t recs = fr[first + cnt] - fr[first];
+            if (k - before >= recs) {
+                before += recs;
+                if (cnt) plain += q.frame_off[first + cnt] - q.frame_off[first];
+                continue;
+            }
+            const uint64_t pos = fr[first] + (k - before);
+            lo = first, hi = first + cnt;
+            while (hi - lo > 1) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (fr[mid] <= pos) lo = mid;
+                else hi = mid;
+            }
+            const uint64_t fb = q.frame_off[lo], fe = q.frame_off[lo + 1];
+            const uint64_t cut = (pos - fr[lo]) * a.max_fragment;  // content bytes before, in the frame
+            const uint64_t left = fe - fb - cut;
+            uvhttp_tls_seal_t o;
+            o.src_off = q.base + fb + cut;
+            o.out_off = a.s_out[s] + plain + (fb - q.frame_off[first]) + cut + k * a.sw[s].over;
+            o.seq = sd.seq + k;
+            o.plain_len = left < a.max_fragment ? (uint32_t)left : a.max_fragment;
+            o.key = (uint16_t)sd.key;
+            o.type = sd.type;
+            o.reserved = 0;
+            a.records[r] = o;
+            break;
+        }
+    }
+}
+
 }  // namespace
 
 // ---- engine ---------------------------------------------------------------------------------
@@ -2831,6 +3022,111 @@ int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames
         const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
         const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
         hipLaunchKernelGGL(k_tls_send_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, p);
+        // the seal kernels read their count from n_total[0]; grids from max_records, capped
+        SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
+                   e->n_total};
+        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
+        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
+        const int tk = tls_timing_begin(e, s);
+        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
+        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
+        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
+        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
+        tls_timing_end(e, tk, s);
+    }
+    const hipError_t h = hipGetLastError();
+    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
+    return UVHTTP_TLS_GPU_OK;
+}
+
+int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames, uint64_t frames_len,
+                              const uvhttp_tls_part_t* parts, uint32_t n_parts,
+                              const uvhttp_tls_send_t* sends, uint32_t n_sends,
+                              const uvhttp_tls_key_t* keys, uint32_t n_keys, uint32_t max_fragment,
+                              uvhttp_tls_seal_t* records, uint32_t max_records,
+                              uvhttp_tls_send_result_t* results, uvhttp_tls_send_summary_t* summary,
+                              uint8_t* out, uint64_t out_cap, void* stream) {
+    if (!e) {  // no engine: there is none without a device
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
+        return UVHTTP_TLS_GPU_EINVAL;
+    }
+    if (!parts || n_parts == 0 || n_parts > UVHTTP_TLS_MAX_PARTS || (!frames && frames_len) ||
+        (!sends && n_sends) || (!keys && n_keys) || (!records && max_records) || (!results && n_sends) ||
+        !summary || (!out && out_cap) || max_fragment > 16384)
+        return UVHTTP_TLS_GPU_EINVAL;
+    if (n_sends > (1u << 26) || max_records > (1u << 28))
+        return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / records", hipSuccess);
+    PartsArgs p;
+    memset(&p, 0, sizeof(p));
+    uint64_t n_frames_all = 0;
+    for (uint32_t k = 0; k < n_parts; ++k) {
+        const uvhttp_tls_part_t& q = parts[k];
+        if (!q.frame_off || !q.runs || ((uintptr_t)q.frame_off & 7u) || ((uintptr_t)q.runs & 3u) ||
+            q.run_stride < 8 || (q.run_stride & 3u) || q.base > frames_len || q.len > frames_len - q.base)
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts: a part's pointers, stride or range", hipSuccess);
+        n_frames_all += q.n_frames;
+        if (n_frames_all > (1u << 28))
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many frames", hipSuccess);
+        p.part[k] = q;
+        p.fbase[k + 1] = p.fbase[k] + q.n_frames + 1;
+        p.bbase[k + 1] = p.bbase[k] + (q.n_frames + 1 + kBlock - 1) / kBlock;
+    }
+    DeviceGuard dev(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!n_sends) {
+        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
+        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
+        return UVHTTP_TLS_GPU_OK;
+    }
+    // the frame scratch holds every part's scan; a part's last workgroup may be partly empty
+    int rc = tls_reserve(e, n_keys, 1, 1, p.fbase[n_parts] + UVHTTP_TLS_MAX_PARTS * kBlock, n_sends);
+    if (rc) return rc;
+    tls_call_begin(e, s);
+    if (n_keys)
+        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
+    p.n_parts = n_parts;
+    p.max_fragment = max_fragment ? max_fragment : 16384u;
+    p.sends = sends;
+    p.n_sends = n_sends;
+    p.n_keys = n_keys;
+    p.sched = e->sched;
+    p.records = records;
+    p.max_records = max_records;
+    p.fr_rec = e->fr_rec;
+    p.fr_bad = e->fr_bad;
+    p.fblk = e->fblk;
+    p.sw = e->send_work;
+    p.sblk = e->sblk;
+    p.s_first = e->s_first;
+    p.s_out = e->s_out;
+    p.n_total = e->n_total;
+    SendArgs q;  // what k_tls_send_scan / k_tls_send_write read
+    memset(&q, 0, sizeof(q));
+    q.sends = sends;
+    q.n_sends = n_sends;
+    q.max_records = max_records;
+    q.results = results;
+    q.summary = summary;
+    q.out_cap = out_cap;
+    q.sw = e->send_work;
+    q.sblk = e->sblk;
+    q.s_first = e->s_first;
+    q.s_out = e->s_out;
+    q.n_total = e->n_total;
+    const uint32_t nfb = p.bbase[n_parts];
+    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_tls_parts_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_scan, dim3(n_parts), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_count, dim3(nsb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, q, nsb);
+    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, q);
+    if (max_records) {
+        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
+        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
+        hipLaunchKernelGGL(k_tls_parts_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, p);
         // the seal kernels read their count from n_total[0]; grids from max_records, capped
         SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
                    e->n_total};

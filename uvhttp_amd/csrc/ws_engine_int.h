@@ -51,6 +51,8 @@ UVWS_INTERNAL void* uvws_utf8_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes,
 UVWS_INTERNAL void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 // The echo of data messages' scratch (ws_echo_gpu.hip), likewise.
 UVWS_INTERNAL void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
+// The server's own CLOSE frames' scratch (ws_close_gpu.hip), likewise.
+UVWS_INTERNAL void* uvws_close_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"
 

@@ -5604,6 +5604,7 @@ enum ScratchId {
     kScrUtf8,     // the frame UTF-8 validator's (utf8_frames_gpu.hip; uvws_utf8_scratch)
     kScrReplies,  // the control replies' (ws_replies_gpu.hip; uvws_replies_scratch)
     kScrEcho,     // the echo of data messages' (ws_echo_gpu.hip; uvws_echo_scratch)
+    kScrClose,    // the server's own CLOSE frames' (ws_close_gpu.hip; uvws_close_scratch)
     kScrCount
 };
 
@@ -6481,6 +6482,9 @@ void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_
 }
 void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
     return scratch_ptr(e, kScrEcho, bytes, s);
+}
+void* uvws_close_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
+    return scratch_ptr(e, kScrClose, bytes, s);
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot

@@ -1109,3 +1109,116 @@ int uvhttp_ws_relay_messages(const uint8_t* wire, uint64_t wire_len,
     free(order);
     return 0;
 }
+
+/* ---- the server's own CLOSE frames (1002 / 1007) for a decoded batch ------------------------ */
+/* The host twin of uvhttp_ws_gpu_close_frames_streams and the statement of its rule
+ * (include/uvhttp_ws_amd.h): what uvhttp_ws_close(NULL, conn, 1002, "protocol error")
+ * (src/uvhttp_websocket.c:627-666) hands to uvhttp_ws_build_frame for every connection whose
+ * decode failed, and a 1007 close with no reason for every connection whose text is not UTF-8. */
+static const char close_reason_1002[] = "protocol error";
+
+/* the code connection s is closed with (0 = no frame); *no_keys when only the key is missing */
+static uint32_t close_code(const uvhttp_ws_stream_t* st, const uvhttp_ws_stream_result_t* res,
+                           const uvhttp_ws_utf8_conn_verdict_t* verdict,
+                           const uvhttp_ws_reply_conn_t* reply, int enabled, int have_keys,
+                           int* no_keys) {
+    *no_keys = 0;
+    if (!enabled) return 0;
+    const int32_t fs = res->first_status;
+    if (fs == UVHTTP_WS_FRAME_ERR_CAPACITY || fs == UVHTTP_WS_FRAME_ERR_LAYOUT ||
+        fs == UVHTTP_WS_FRAME_ERR_DEVICE)
+        return 0;
+    if (reply != NULL && reply->closed) return 0;
+    uint32_t code = 0;
+    if (verdict != NULL && verdict->status == UVHTTP_WS_UTF8_INVALID) code = 1007;
+    else if (fs < 0) code = 1002;
+    if (code != 0 && !st->is_server && !have_keys) {
+        *no_keys = 1;
+        return 0;
+    }
+    return code;
+}
+
+static uint32_t close_frame_len(uint32_t code, int masked) {
+    if (code == 0) return 0;
+    return 2u + (masked ? 4u : 0u) + 2u + (code == 1002 ? (uint32_t)(sizeof(close_reason_1002) - 1) : 0u);
+}
+
+int uvhttp_ws_close_frames(const uvhttp_ws_stream_t* streams, const uvhttp_ws_stream_result_t* results,
+                           uint32_t n_streams, const uvhttp_ws_utf8_conn_verdict_t* verdict,
+                           const uvhttp_ws_reply_conn_t* reply_conn, const uint8_t* enable,
+                           const uint32_t* mask_keys, uint32_t flags, uint8_t* out, uint64_t out_cap,
+                           uint64_t* out_off, uint32_t* runs, uint32_t run_stride,
+                           uint32_t* const* clear_runs, const uint32_t* clear_stride, uint32_t n_clear,
+                           uvhttp_ws_close_conn_t* conn, uvhttp_ws_close_summary_t* summary) {
+    if (out_off == NULL || summary == NULL || (out == NULL && out_cap != 0) || flags != 0 ||
+        (n_streams != 0 && (streams == NULL || results == NULL || conn == NULL)) ||
+        n_streams > (1u << 31) || (runs != NULL && (run_stride < 8 || (run_stride & 3u))) ||
+        n_clear > UVHTTP_WS_CLOSE_MAX_CLEAR || (n_clear != 0 && (clear_runs == NULL || clear_stride == NULL)))
+        return -1;
+    for (uint32_t k = 0; k < n_clear; ++k)
+        if (clear_runs[k] == NULL || clear_stride[k] < 8 || (clear_stride[k] & 3u)) return -1;
+    memset(summary, 0, sizeof(*summary));
+    /* size, then emit */
+    uint64_t bytes = 0;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        int nk;
+        const uint32_t code = close_code(&streams[s], &results[s], verdict ? &verdict[s] : NULL,
+                                         reply_conn ? &reply_conn[s] : NULL,
+                                         enable == NULL || enable[s] != 0, mask_keys != NULL, &nk);
+        bytes += close_frame_len(code, !streams[s].is_server);
+        summary->n_1002 += code == 1002;
+        summary->n_1007 += code == 1007;
+    }
+    summary->n_closes = summary->n_1002 + summary->n_1007;
+    summary->out_bytes = bytes;
+    const int fits = bytes <= out_cap;
+    summary->status = fits ? UVHTTP_WS_CLOSE_OK : UVHTTP_WS_CLOSE_ERR_CAPACITY;
+    uint64_t at = 0;
+    uint32_t j = 0;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        uvhttp_ws_close_conn_t* r = &conn[s];
+        memset(r, 0, sizeof(*r));
+        uint32_t* run = runs ? (uint32_t*)((char*)runs + (size_t)s * run_stride) : NULL;
+        if (!fits) {
+            r->status = UVHTTP_WS_CLOSE_ERR_CAPACITY;
+            out_off[s] = 0;
+            if (run) run[0] = run[1] = 0;
+            continue;
+        }
+        int nk;
+        const int masked = !streams[s].is_server;
+        const uint32_t code = close_code(&streams[s], &results[s], verdict ? &verdict[s] : NULL,
+                                         reply_conn ? &reply_conn[s] : NULL,
+                                         enable == NULL || enable[s] != 0, mask_keys != NULL, &nk);
+        const uint32_t len = close_frame_len(code, masked);
+        if (nk) r->status = UVHTTP_WS_CLOSE_NO_KEYS;
+        if (run) {
+            run[0] = j;
+            run[1] = code ? 1u : 0u;
+        }
+        if (code) {
+            const uint32_t key = masked ? mask_keys[s] : 0u;
+            const uint32_t plen = len - (masked ? 6u : 2u);
+            uint8_t* o = out + at;
+            uint8_t* p = o + (masked ? 6 : 2);
+            o[0] = (uint8_t)(0x80u | UVHTTP_WS_OPCODE_CLOSE);
+            o[1] = (uint8_t)((masked ? 0x80u : 0u) | plen);
+            if (masked)
+                for (int k = 0; k < 4; ++k) o[2 + k] = (uint8_t)(key >> (8 * k));
+            p[0] = (uint8_t)(code >> 8);
+            p[1] = (uint8_t)code;
+            for (uint32_t b = 2; b < plen; ++b) p[b] = (uint8_t)close_reason_1002[b - 2];
+            for (uint32_t b = 0; b < plen; ++b) p[b] ^= (uint8_t)(key >> (8 * (b & 3)));
+            r->code = code;
+            r->out_len = len;
+            out_off[j++] = at;
+            at += len;
+            if (code == 1007)
+                for (uint32_t k = 0; k < n_clear; ++k)
+                    ((uint32_t*)((char*)clear_runs[k] + (size_t)s * clear_stride[k]))[1] = 0;
+        }
+    }
+    for (uint64_t k = fits ? j : n_streams; k <= n_streams; ++k) out_off[k] = fits ? at : 0;
+    return 0;
+}
