@@ -55,6 +55,11 @@ $(BUILD)/ws_close_gpu.o: uvhttp_amd/csrc/ws_close_gpu.hip include/uvhttp_ws_amd.
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
+# the fail points (cut a connection at its first violation) after a decode: likewise one object for both
+$(BUILD)/ws_fail_gpu.o: uvhttp_amd/csrc/ws_fail_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
 $(BUILD)/tls_gpu.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h $(DEVICE_GUARD)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -88,12 +93,12 @@ $(BUILD)/ws_batcher_group.o: uvhttp_amd/csrc/ws_batcher_group.cpp include/uvhttp
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -fPIC -std=c++17 -Iinclude -Wall -Wextra -Werror -c -o $@ $<
 
-$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
+$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/ws_fail_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
         $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
-$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
+$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/ws_fail_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
             $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -103,7 +108,7 @@ oracle:
 
 # test programs: the C1 libuv echo harness (against the product library) and the
 # ASan/UBSan builds of the host decoder + oracle (tests/c/Makefile)
-ctests: $(LIB) oracle tests/c/_build/close_check
+ctests: $(LIB) oracle tests/c/_build/close_check tests/c/_build/fail_check
 	$(MAKE) -C tests/c
 
 # the server's own CLOSE frames (ws_host.c: uvhttp_ws_close_frames) under ASan/UBSan, in a program
@@ -112,6 +117,13 @@ tests/c/_build/close_check: tests/c/close_check.c uvhttp_amd/csrc/ws_host.c incl
 	@mkdir -p tests/c/_build
 	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
 	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/close_check.c uvhttp_amd/csrc/ws_host.c
+
+# the fail points (ws_host.c: uvhttp_ws_fail_points) under ASan/UBSan, likewise
+# (tests/c/fail_check.c, run by tests/test_fail_points_host.py)
+tests/c/_build/fail_check: tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
+	@mkdir -p tests/c/_build
+	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
+	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c
 
 # measurement tools run on the GPU box (PCIe ceilings beside the live-shape e2e)
 probes: tools/bin/pcie_probe tools/bin/copy_probe
@@ -125,7 +137,7 @@ tools/bin/copy_probe: tools/copy_probe.cpp $(BUILD)/ws_host.o
 	@mkdir -p tools/bin
 	g++ -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude -o $@ $^ -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
-asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip uvhttp_amd/csrc/utf8_frames_gpu.hip uvhttp_amd/csrc/ws_replies_gpu.hip uvhttp_amd/csrc/ws_echo_gpu.hip uvhttp_amd/csrc/ws_close_gpu.hip
+asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip uvhttp_amd/csrc/utf8_frames_gpu.hip uvhttp_amd/csrc/ws_replies_gpu.hip uvhttp_amd/csrc/ws_echo_gpu.hip uvhttp_amd/csrc/ws_close_gpu.hip uvhttp_amd/csrc/ws_fail_gpu.hip
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_gpu.s uvhttp_amd/csrc/ws_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/tls_gpu.s uvhttp_amd/csrc/tls_gpu.hip
@@ -134,6 +146,7 @@ asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_replies_gpu.s uvhttp_amd/csrc/ws_replies_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_echo_gpu.s uvhttp_amd/csrc/ws_echo_gpu.hip
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_close_gpu.s uvhttp_amd/csrc/ws_close_gpu.hip
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_fail_gpu.s uvhttp_amd/csrc/ws_fail_gpu.hip
 
 clean:
 	rm -rf $(BUILD) uvhttp_amd/lib

@@ -1194,6 +1194,110 @@ int uvhttp_ws_close_frames(const uvhttp_ws_stream_t* streams, const uvhttp_ws_st
                            uint32_t* const* clear_runs, const uint32_t* clear_stride, uint32_t n_clear,
                            uvhttp_ws_close_conn_t* conn, uvhttp_ws_close_summary_t* summary);
 
+/* ---- fail points: stop a connection at its first violation ---------------------------------- */
+/* One pass between the judging (decode, validate_utf8_streams) and the sends (echo_messages or
+ * relay_messages, control_replies, close_frames).  It finds the frame at which a server that
+ * follows RFC 6455 §7.1.7 fails each connection, and rewrites the two outcome tables into what
+ * that server would have seen had the decode stopped there.  The send passes then run unchanged
+ * on the rewritten tables: a failed connection sends its echoes and replies before the violation
+ * and then its close; a bad CLOSE is not echoed (`closed` stays 0, so close_frames sends the
+ * 1002); an invalid sender's message never enters its room; no PING after the cut gets a PONG.
+ *
+ * Considered frames of connection s: desc[first_frame, first_frame + n_delivered), clipped to
+ * max_frames as the echo clips them.  c = the first considered CLOSE with status OK, if any.
+ *
+ * CLOSE violation (only with UVHTTP_WS_FAIL_CHECK_CLOSE, only frame c; RFC 6455 §7.4, the
+ * reference checks neither): payload_len == 1 is reason CLOSE_LEN; payload_len >= 2 with an
+ * invalid big-endian code in payload[0, 2) is reason CLOSE_CODE.  Valid codes are 1000-1003,
+ * 1007-1014 and 3000-4999: RFC 6455 §7.4.1-2 plus the IANA-registered 1012-1014, this project's
+ * choice.  Either reason fails the connection with 1002 at frame c.  If frame c has payload_len >=
+ * 2 and its payload range is not inside [0, wire_len), the connection gets status
+ * UVHTTP_WS_FAIL_BAD_RANGE (a caller error): reason NONE, no cut, both tables copied as they are.
+ * Nothing outside the wire is read, and only those 2 bytes of one frame per connection ever are.
+ * UTF-8 violation: d_verdict[s].status == UVHTTP_WS_UTF8_INVALID, u = first_invalid is a
+ * considered frame and u <= c (or there is no c): 1007 at frame u, reason UTF8.  A violation after
+ * the first delivered CLOSE is no failure: the server stopped at the CLOSE (what close_frames
+ * expresses through `closed`).
+ * Precedence: the earlier frame wins; on the same frame (a CLOSE with a bad code and a reason
+ * that is not UTF-8) 1002 wins.
+ * Decode failure: no cut and first_status < 0: reason DECODE, code 1002, frame = first_frame +
+ * n_delivered.  Nothing is rewritten, the decode already stopped there.
+ * Not judged: connections with d_enable[s] == 0 and connections whose result is ERR_CAPACITY,
+ * ERR_LAYOUT or ERR_DEVICE are copied unchanged, reason NONE.
+ *
+ * A cut at frame k.  d_results_out[s] is a copy with n_delivered = k - first_frame, n_frames =
+ * n_delivered + 1, status = UVHTTP_ERROR_INVALID_PARAM and first_status = UVHTTP_WS_FRAME_ERR_UTF8
+ * or UVHTTP_WS_FRAME_ERR_CLOSE; every other field (consumed_bytes, pending_bytes, ... of the whole
+ * decode) is copied.  d_verdict_out[s] is a copy, except that a connection cut by a CLOSE
+ * violation at or before its first_invalid, or (cut or not) whose first_invalid lies after c, gets
+ * status VALID, first_invalid 0xFFFFFFFF and a zero state, the verdict over the kept frames
+ * (n_text_frames is copied).  d_fail[s] names the frame, the code, the reason, and n_dropped = the
+ * considered frames at or after the cut.  close_frames over the rewritten tables sends
+ * d_fail[s].code: 1007 for first_status ERR_UTF8 (the verdict stays INVALID), 1002 for ERR_CLOSE.
+ *
+ * One wart.  The echo reports the bytes of the cut message's earlier fragments as "open"; that
+ * carry is dropped with the connection, as a session driver drops any leaver's carry.
+ * Out of scope: uvhttp_ws_deliver_stream keeps taking the ORIGINAL d_results; host delivery from
+ * the rewritten table is not supported (its consumed_bytes / pending_bytes are the whole decode's).
+ *
+ * d_results_out may be d_results and d_verdict_out may be d_verdict (in place); any other overlap
+ * is unspecified.  d_verdict and d_verdict_out are both given or both NULL; d_enable may be NULL.
+ * Device pointers: d_desc, d_results, d_results_out and d_summary 8-byte aligned, the others 4
+ * (d_wire, d_enable 1).  EINVAL for NULL or misaligned arguments, unknown flags, max_frames > 2^28,
+ * n_streams > 2^31.  Asynchronous on `stream` under the engine's stream rule; 4 bytes of engine
+ * scratch per descriptor and per connection, grown on demand: graph-capturable once one uncaptured
+ * call of the same or a larger shape has been made.  Reads one 32-byte descriptor per frame, one
+ * 64 + 16-byte entry per connection and 2 wire bytes per closing connection. */
+#define UVHTTP_WS_FRAME_ERR_UTF8 (-12)   /* first_status of a connection cut at invalid UTF-8 */
+#define UVHTTP_WS_FRAME_ERR_CLOSE (-13)  /* ... at a CLOSE with a 1-byte payload or a bad code */
+
+#define UVHTTP_WS_FAIL_CHECK_CLOSE 0x1u  /* flags: judge the first CLOSE's payload length and code */
+
+#define UVHTTP_WS_FAIL_OK 0
+#define UVHTTP_WS_FAIL_BAD_RANGE 2       /* the first CLOSE's payload range lies outside the wire */
+
+#define UVHTTP_WS_FAIL_NONE 0            /* reasons */
+#define UVHTTP_WS_FAIL_DECODE 1
+#define UVHTTP_WS_FAIL_UTF8 2
+#define UVHTTP_WS_FAIL_CLOSE_LEN 3
+#define UVHTTP_WS_FAIL_CLOSE_CODE 4
+
+typedef struct {            /* 16 B, one per connection, device-written */
+    uint32_t frame;         /* desc index (absolute) of the fail point, 0xFFFFFFFF if none */
+    uint32_t n_dropped;     /* considered frames at or after a cut (0 for DECODE) */
+    uint16_t code;          /* 0, 1002 or 1007 */
+    uint8_t reason;         /* UVHTTP_WS_FAIL_NONE / DECODE / UTF8 / CLOSE_LEN / CLOSE_CODE */
+    uint8_t status;         /* UVHTTP_WS_FAIL_OK or UVHTTP_WS_FAIL_BAD_RANGE */
+    uint32_t reserved;
+} uvhttp_ws_fail_conn_t;
+
+typedef struct {            /* 32 B */
+    uint64_t n_dropped;     /* sum over the connections */
+    uint32_t n_decode;      /* connections per reason */
+    uint32_t n_utf8;
+    uint32_t n_close_len;
+    uint32_t n_close_code;
+    uint32_t n_bad_range;   /* connections with status BAD_RANGE */
+    uint32_t first_failed;  /* lowest connection with a reason, 0xFFFFFFFF if none */
+} uvhttp_ws_fail_summary_t;
+
+int uvhttp_ws_gpu_fail_points_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire, uint64_t wire_len,
+                                      const uvhttp_ws_frame_desc_t* d_desc, uint32_t max_frames,
+                                      const uvhttp_ws_stream_result_t* d_results, uint32_t n_streams,
+                                      const uvhttp_ws_utf8_conn_verdict_t* d_verdict, const uint8_t* d_enable,
+                                      uint32_t flags, uvhttp_ws_stream_result_t* d_results_out,
+                                      uvhttp_ws_utf8_conn_verdict_t* d_verdict_out,
+                                      uvhttp_ws_fail_conn_t* d_fail, uvhttp_ws_fail_summary_t* d_summary,
+                                      void* stream);
+/* Host twin (plain C, host copies of the same tables): all connections of the call at once and
+ * the same four outputs, byte for byte; the statement of the rule.  Returns 0, or -1 for an
+ * argument the device call answers with EINVAL. */
+int uvhttp_ws_fail_points(const uint8_t* wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* desc,
+                          uint32_t max_frames, const uvhttp_ws_stream_result_t* results, uint32_t n_streams,
+                          const uvhttp_ws_utf8_conn_verdict_t* verdict, const uint8_t* enable, uint32_t flags,
+                          uvhttp_ws_stream_result_t* results_out, uvhttp_ws_utf8_conn_verdict_t* verdict_out,
+                          uvhttp_ws_fail_conn_t* fail, uvhttp_ws_fail_summary_t* summary);
+
 /* ---- host-memory pipeline (libuv read buffers in, decoded payloads out) ---------------- */
 /* A pipeline owns `depth` slots.  Each slot = a pinned host staging buffer (the caller
  * writes masked frames there, e.g. hands it out from the libuv alloc callback) and a device

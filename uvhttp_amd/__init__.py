@@ -33,6 +33,7 @@ FRAME_STATUS = {
     0: "OK", 1: "INCOMPLETE", 2: "SKIPPED", -1: "ERR_PARSE", -2: "ERR_RSV", -3: "ERR_CONTROL",
     -4: "ERR_UNMASKED", -5: "ERR_TOO_BIG", -6: "ERR_BUFFER", -7: "ERR_FRAGMENT",
     -8: "ERR_MESSAGE", -9: "ERR_LAYOUT", -10: "ERR_CAPACITY", -11: "ERR_DEVICE",
+    -12: "ERR_UTF8", -13: "ERR_CLOSE",  # written by the fail points only, never by a decode
 }
 FLAG_FIN, FLAG_MASK, FLAG_MSG_END = 0x01, 0x02, 0x20
 
@@ -158,6 +159,31 @@ class CloseSummary(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k in ("out_bytes", "n_closes", "n_1002", "n_1007", "status")}
+
+
+FRAME_ERR_UTF8, FRAME_ERR_CLOSE = -12, -13  # UVHTTP_WS_FRAME_ERR_*: first_status of a cut connection
+FAIL_CHECK_CLOSE = 0x1  # UVHTTP_WS_FAIL_CHECK_CLOSE
+FAIL_OK, FAIL_BAD_RANGE = 0, 2  # UVHTTP_WS_FAIL_* statuses
+FAIL_NONE, FAIL_DECODE, FAIL_UTF8, FAIL_CLOSE_LEN, FAIL_CLOSE_CODE = range(5)  # ... reasons
+
+
+class FailConn(C.Structure):
+    """uvhttp_ws_fail_conn_t (16 B)."""
+    _fields_ = [("frame", C.c_uint32), ("n_dropped", C.c_uint32), ("code", C.c_uint16),
+                ("reason", C.c_uint8), ("status", C.c_uint8), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("frame", "n_dropped", "code", "reason", "status")}
+
+
+class FailSummary(C.Structure):
+    """uvhttp_ws_fail_summary_t (32 B)."""
+    _fields_ = [("n_dropped", C.c_uint64), ("n_decode", C.c_uint32), ("n_utf8", C.c_uint32),
+                ("n_close_len", C.c_uint32), ("n_close_code", C.c_uint32), ("n_bad_range", C.c_uint32),
+                ("first_failed", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 TLS_MAX_PARTS = 8  # UVHTTP_TLS_MAX_PARTS
@@ -469,6 +495,9 @@ def load_library(path: str) -> C.CDLL:
                                                          vp, u32, vp, vp, u32, vp, vp, vp]),
         "uvhttp_ws_close_frames": (C.c_int, [vp, vp, u32, vp, vp, vp, vp, u32, vp, u64, vp, vp, u32, vp,
                                              vp, u32, vp, vp]),
+        "uvhttp_ws_gpu_fail_points_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, vp, vp,
+                                                        vp, vp, vp]),
+        "uvhttp_ws_fail_points": (C.c_int, [vp, u64, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp]),
         "uvhttp_ws_gen_frame_stride": (u64, [u64]),
         "uvhttp_ws_gpu_pipeline_create": (C.c_int, [C.c_int, C.c_int, u64, u32, C.POINTER(vp)]),
         "uvhttp_ws_gpu_pipeline_free": (None, [vp]),
@@ -709,6 +738,30 @@ def close_frames(streams, results, n_streams, verdict=None, reply_conn=None, ena
     sd = summ.as_dict()
     n = int(out_off[n_streams])
     return out[:n].tobytes(), out_off, runs, [conn[k].as_dict() for k in range(n_streams)], sd
+
+
+def fail_points(wire, desc, max_frames, results, n_streams, verdict=None, enable=None, flags=0,
+                in_place=False, wire_len=None):
+    """uvhttp_ws_fail_points: the host twin of GpuEngine.fail_points_streams.  wire / desc / results
+    / verdict = contiguous numpy arrays holding the bytes and the C structs (any dtype), enable =
+    uint8[n_streams] or None.  in_place: results and verdict are rewritten themselves (and
+    returned).  Returns (results_out, verdict_out or None, fail, summary): numpy uint8 arrays of
+    n_streams 64-, 16- and 16-byte entries and the 32 summary bytes (FailConn / FailSummary)."""
+    import numpy as np
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    m = max(1, n_streams)
+    res_out = results if in_place else np.zeros(m * C.sizeof(StreamResult) // 8, dtype=np.uint64).view(np.uint8)
+    ver_out = None
+    if verdict is not None:
+        ver_out = verdict if in_place else np.zeros(m * 16, dtype=np.uint8)
+    fail = np.zeros(m * C.sizeof(FailConn), dtype=np.uint8)
+    summ = np.zeros(C.sizeof(FailSummary) // 8, dtype=np.uint64).view(np.uint8)
+    rc = lib().uvhttp_ws_fail_points(ptr(wire), len(wire) if wire_len is None else wire_len, ptr(desc), max_frames,
+                                     ptr(results), n_streams, ptr(verdict), ptr(enable), flags, ptr(res_out),
+                                     ptr(ver_out), ptr(fail), ptr(summ))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_fail_points: bad argument")
+    return res_out, ver_out, fail, summ
 
 
 def echo_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, mask_keys=None,
@@ -1250,6 +1303,45 @@ class GpuEngine:
     def read_close_summary(summary) -> dict:
         raw = summary[: C.sizeof(CloseSummary)].cpu().numpy().tobytes()
         return CloseSummary.from_buffer_copy(raw).as_dict()
+
+    def fail_points_streams(self, wire, desc, max_frames, results, n_streams, verdict=None, enable=None,
+                            flags=0, results_out=None, verdict_out=None, fail=None, summary=None,
+                            wire_len=None, stream=None):
+        """uvhttp_ws_gpu_fail_points_streams after a stream decode and validate_utf8_streams over
+        the same device tensors, before the send passes: every connection's fail point, and the
+        result and verdict tables rewritten to stop there.  results_out / verdict_out may be
+        results / verdict themselves (in place).  Returns (results_out, verdict_out or None, fail,
+        summary) device tensors: n_streams 64-byte results, 16-byte verdicts and 16-byte
+        uvhttp_ws_fail_conn_t, and the 32-byte uvhttp_ws_fail_summary_t."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        m = max(1, n_streams)
+        if results_out is None:
+            results_out = t.zeros(m * C.sizeof(StreamResult), dtype=t.uint8, device=dev)
+        if verdict_out is None and verdict is not None:
+            verdict_out = t.zeros(m * C.sizeof(Utf8ConnVerdict), dtype=t.uint8, device=dev)
+        if fail is None:
+            fail = t.zeros(m * C.sizeof(FailConn), dtype=t.uint8, device=dev)
+        if summary is None:
+            summary = t.zeros(C.sizeof(FailSummary), dtype=t.uint8, device=dev)
+        self._check(self._L.uvhttp_ws_gpu_fail_points_streams(
+            self.h, self._ptr(wire), wire.numel() if wire_len is None else wire_len, self._ptr(desc), max_frames,
+            self._ptr(results), n_streams, self._ptr(verdict), self._ptr(enable), flags, self._ptr(results_out),
+            self._ptr(verdict_out), self._ptr(fail), self._ptr(summary), self._stream(stream)),
+            "fail_points_streams")
+        return results_out, verdict_out, fail, summary
+
+    @staticmethod
+    def read_fail_conns(fail, n):
+        """host copy of the first n fail entries -> [dict] (FailConn.as_dict)"""
+        sz = C.sizeof(FailConn)
+        raw = fail[: n * sz].cpu().numpy().tobytes()
+        return [FailConn.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_fail_summary(summary) -> dict:
+        raw = summary[: C.sizeof(FailSummary)].cpu().numpy().tobytes()
+        return FailSummary.from_buffer_copy(raw).as_dict()
 
     def _echo_out(self, n_streams, max_echoes, out_cap, out, out_off, open_off, conn, summary):
         t = self.torch

@@ -53,6 +53,8 @@ UVWS_INTERNAL void* uvws_replies_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t byt
 UVWS_INTERNAL void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 // The server's own CLOSE frames' scratch (ws_close_gpu.hip), likewise.
 UVWS_INTERNAL void* uvws_close_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
+// The fail points' scratch (ws_fail_gpu.hip), likewise.
+UVWS_INTERNAL void* uvws_fail_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s);
 
 }  // extern "C"
 

@@ -5605,6 +5605,7 @@ enum ScratchId {
     kScrReplies,  // the control replies' (ws_replies_gpu.hip; uvws_replies_scratch)
     kScrEcho,     // the echo of data messages' (ws_echo_gpu.hip; uvws_echo_scratch)
     kScrClose,    // the server's own CLOSE frames' (ws_close_gpu.hip; uvws_close_scratch)
+    kScrFail,     // the fail points' (ws_fail_gpu.hip; uvws_fail_scratch)
     kScrCount
 };
 
@@ -6485,6 +6486,9 @@ void* uvws_echo_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s
 }
 void* uvws_close_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
     return scratch_ptr(e, kScrClose, bytes, s);
+}
+void* uvws_fail_scratch(uvhttp_ws_gpu_engine_t* e, uint64_t bytes, hipStream_t s) {
+    return scratch_ptr(e, kScrFail, bytes, s);
 }
 
 // The summary-only kernels' fragment state machine is exact for a stride batch when every slot

@@ -1222,3 +1222,107 @@ int uvhttp_ws_close_frames(const uvhttp_ws_stream_t* streams, const uvhttp_ws_st
     for (uint64_t k = fits ? j : n_streams; k <= n_streams; ++k) out_off[k] = fits ? at : 0;
     return 0;
 }
+
+/* ---- fail points: stop a connection at its first violation ---------------------------------- */
+/* The host twin of uvhttp_ws_gpu_fail_points_streams and the statement of its rule
+ * (include/uvhttp_ws_amd.h). */
+static int fail_code_valid(uint32_t code) {
+    return (code >= 1000 && code <= 1003) || (code >= 1007 && code <= 1014) || (code >= 3000 && code <= 4999);
+}
+
+int uvhttp_ws_fail_points(const uint8_t* wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* desc,
+                          uint32_t max_frames, const uvhttp_ws_stream_result_t* results, uint32_t n_streams,
+                          const uvhttp_ws_utf8_conn_verdict_t* verdict, const uint8_t* enable, uint32_t flags,
+                          uvhttp_ws_stream_result_t* results_out, uvhttp_ws_utf8_conn_verdict_t* verdict_out,
+                          uvhttp_ws_fail_conn_t* fail, uvhttp_ws_fail_summary_t* summary) {
+    const uint32_t none = 0xFFFFFFFFu;
+    if (desc == NULL || results == NULL || results_out == NULL || fail == NULL || summary == NULL ||
+        (wire == NULL && wire_len != 0) || (verdict == NULL) != (verdict_out == NULL))
+        return -1;
+    if (((uintptr_t)desc & 7u) || ((uintptr_t)results & 7u) || ((uintptr_t)results_out & 7u) ||
+        ((uintptr_t)summary & 7u) || ((uintptr_t)verdict & 3u) || ((uintptr_t)verdict_out & 3u) ||
+        ((uintptr_t)fail & 3u))
+        return -1;
+    if ((flags & ~UVHTTP_WS_FAIL_CHECK_CLOSE) != 0 || max_frames > (1u << 28) || n_streams > (1u << 31)) return -1;
+    uvhttp_ws_fail_summary_t sum;
+    memset(&sum, 0, sizeof(sum));
+    sum.first_failed = none;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        uvhttp_ws_stream_result_t r = results[s];  /* copies first: the outputs may be the inputs */
+        uvhttp_ws_utf8_conn_verdict_t v;
+        memset(&v, 0, sizeof(v));
+        if (verdict != NULL) v = verdict[s];
+        uvhttp_ws_fail_conn_t f;
+        memset(&f, 0, sizeof(f));
+        f.frame = none;
+        const int32_t fs = r.first_status;
+        const int judged = (enable == NULL || enable[s] != 0) && fs != UVHTTP_WS_FRAME_ERR_CAPACITY &&
+                           fs != UVHTTP_WS_FRAME_ERR_LAYOUT && fs != UVHTTP_WS_FRAME_ERR_DEVICE;
+        if (judged) {
+            const uint32_t ff = r.first_frame;
+            uint32_t nd = r.n_delivered;
+            if (ff >= max_frames) nd = 0;
+            else if (nd > max_frames - ff) nd = max_frames - ff;
+            uint32_t c = none;
+            for (uint32_t i = 0; i < nd && c == none; ++i)
+                if (desc[ff + i].opcode == UVHTTP_WS_OPCODE_CLOSE && desc[ff + i].status == UVHTTP_WS_FRAME_OK)
+                    c = ff + i;
+            uint32_t k = none, reason = UVHTTP_WS_FAIL_NONE;
+            int bad = 0;
+            if ((flags & UVHTTP_WS_FAIL_CHECK_CLOSE) && c != none) {
+                const uint64_t len = desc[c].payload_len, off = desc[c].payload_off;
+                if (len == 1) {
+                    reason = UVHTTP_WS_FAIL_CLOSE_LEN;
+                } else if (len >= 2) {
+                    if (len > wire_len || off > wire_len - len) bad = 1;
+                    else if (!fail_code_valid((uint32_t)wire[off] << 8 | wire[off + 1]))
+                        reason = UVHTTP_WS_FAIL_CLOSE_CODE;
+                }
+                if (reason != UVHTTP_WS_FAIL_NONE) k = c;
+            }
+            if (bad) {
+                f.status = UVHTTP_WS_FAIL_BAD_RANGE;
+                ++sum.n_bad_range;
+            } else {
+                const uint32_t u = v.first_invalid;
+                const int close_cut = k != none;
+                if (verdict != NULL && v.status == UVHTTP_WS_UTF8_INVALID && u >= ff && u - ff < nd &&
+                    (c == none || u <= c) && (k == none || u < k)) {
+                    k = u;
+                    reason = UVHTTP_WS_FAIL_UTF8;
+                }
+                if (k != none) {
+                    f.frame = k;
+                    f.n_dropped = nd - (k - ff);
+                    f.code = reason == UVHTTP_WS_FAIL_UTF8 ? 1007 : 1002;
+                    r.n_delivered = k - ff;
+                    r.n_frames = r.n_delivered + 1;
+                    r.status = UVHTTP_ERROR_INVALID_PARAM;
+                    r.first_status = reason == UVHTTP_WS_FAIL_UTF8 ? UVHTTP_WS_FRAME_ERR_UTF8 : UVHTTP_WS_FRAME_ERR_CLOSE;
+                } else if (fs < 0) {
+                    reason = UVHTTP_WS_FAIL_DECODE;
+                    f.frame = r.first_frame + r.n_delivered;
+                    f.code = 1002;
+                }
+                f.reason = (uint8_t)reason;
+                /* the verdict over the kept frames */
+                if (verdict != NULL && u != none && c != none && (u > c || (close_cut && u == c))) {
+                    v.status = UVHTTP_WS_UTF8_VALID;
+                    v.first_invalid = none;
+                    memset(&v.state, 0, sizeof(v.state));
+                }
+                sum.n_dropped += f.n_dropped;
+                sum.n_decode += reason == UVHTTP_WS_FAIL_DECODE;
+                sum.n_utf8 += reason == UVHTTP_WS_FAIL_UTF8;
+                sum.n_close_len += reason == UVHTTP_WS_FAIL_CLOSE_LEN;
+                sum.n_close_code += reason == UVHTTP_WS_FAIL_CLOSE_CODE;
+                if (reason != UVHTTP_WS_FAIL_NONE && sum.first_failed == none) sum.first_failed = s;
+            }
+        }
+        results_out[s] = r;
+        if (verdict_out != NULL) verdict_out[s] = v;
+        fail[s] = f;
+    }
+    *summary = sum;
+    return 0;
+}
