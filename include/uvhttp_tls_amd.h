@@ -225,7 +225,9 @@ int uvhttp_tls_gpu_open_records(uvhttp_tls_gpu_engine_t* eng, const uint8_t* wir
 /* Seal records (the send side, and the bench's input generator).  Record i: header (type 23
  * for TLS 1.3, `type` for TLS 1.2), TLS 1.2 AES-GCM explicit nonce = be64(seq), ciphertext, tag; the
  * TLS 1.3 inner plaintext is content || type with no padding.  Device pointers throughout;
- * records must not overlap src. */
+ * records must not overlap src, with one exception: src = out and src_off = out_off + 5 (+ 8 for
+ * the explicit nonce of TLS 1.2 AES-GCM) for every record seals in place, the content lying where
+ * its ciphertext will (uvhttp_tls_gpu_seal_parts_coalesced rests on this). */
 /* The TLS -> WebSocket hand-off on the device.  For every connection s: the ws_prefix bytes
  * at prefix_src[prefix_off[s]] (its recv_buffer[0, recv_buffer_pos), staged by the caller;
  * prefix_src may be NULL when every ws_prefix is 0) are copied to out[out_off - ws_prefix,
@@ -354,6 +356,59 @@ int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* eng, const uint8_t* frame
                               uvhttp_tls_send_result_t* results,
                               uvhttp_tls_send_summary_t* summary, uint8_t* out, uint64_t out_cap,
                               void* stream);
+
+/* Seal several parts per send with the frames COALESCED into full records: what a server that
+ * corks its writes puts on the wire.  TLS carries a byte stream, so a receiver cannot tell where
+ * the sender's write calls ended; seal_frames and seal_parts cut every frame on its own because
+ * the reference's mbedtls_ssl_write loop does, this call does not.  The arguments are seal_parts',
+ * argument for argument (frames = the send arena, parts in host memory with device pointers
+ * inside, sends[s] supplies seq, key and type and its first_frame / n_frames are ignored).
+ *
+ * Stream.  Send s's stream is the bytes of part 0's run, then part 1's run, ...  A run whose
+ * offsets do not decrease is the one range frames[base_p + frame_off_p[first], base_p +
+ * frame_off_p[first + n]), so a stream has at most n_parts segments; empty frames and empty runs
+ * contribute nothing.  Frame boundaries mean nothing to the cutting: a record may hold many
+ * frames, and a frame (its header too) may lie across two records.
+ *
+ * Cutting, numbering, layout.  With B the stream's length the send gets ceil(B / max_fragment)
+ * records, every one of max_fragment content bytes except the last (max_fragment 1..16384, 0 =
+ * 16384); B = 0 gives no record and status 0.  The records are numbered seq, seq + 1, ... and lie
+ * back to back in out, sends in index order.  results[s] and summary are seal_frames' structs with
+ * seal_frames' meaning: plain_len = B, next_seq = seq + n_records.  The bytes of a record are
+ * exactly uvhttp_tls_gpu_seal_records' for the same (key, seq, type, content).
+ *
+ * records[r] describes record r with src_off = out_off + 5 + the key's explicit-nonce length (8
+ * for TLS 1.2 AES-GCM, otherwise 0): the place in `out` where the content was gathered before it
+ * was sealed, and where its ciphertext now lies.  So records[] is a valid
+ * uvhttp_tls_gpu_seal_records input over any buffer that holds the streams at those offsets (the
+ * plaintext is no longer in out after the call).
+ *
+ * Per-send failures: ERR_KEY, then ERR_RANGE, exactly as seal_parts defines them.  A failed send
+ * has 0 records and next_seq = seq, not a byte of out is written for it, and the other sends are
+ * not affected; a bad frame outside every run harms nobody.  Capacity: seal_frames' rule.  If the
+ * records or bytes of the sends without an error of their own exceed max_records / out_cap, every
+ * such send reports ERR_CAPACITY, nothing is written to out or records (no content is gathered
+ * either), and summary holds the sizes to call again with.
+ *
+ * Overlap and broadcast.  Parts may overlap, the same table may be listed twice and sends may name
+ * the same frames under N keys: frames is only read.  out is written and then sealed in place, so
+ * it may not overlap frames.
+ *
+ * EINVAL: everything seal_parts refuses, and [out, out + out_cap) intersecting [frames, frames +
+ * frames_len).  n_sends = 0 returns OK with a zeroed summary.  Asynchronous on `stream`, no host
+ * synchronisation, scratch in the engine (seal_parts' plus 128 bytes of segment table per send and
+ * 16 bytes per entry of records[]): graph-capturable after one uncaptured call of the same or a
+ * larger shape.  There is no seal_frames-shaped variant: one part whose runs points at
+ * &sends[0].first_frame with run_stride = 32 (sizeof(uvhttp_tls_send_t)) expresses it. */
+int uvhttp_tls_gpu_seal_parts_coalesced(uvhttp_tls_gpu_engine_t* eng, const uint8_t* frames,
+                                        uint64_t frames_len, const uvhttp_tls_part_t* parts,
+                                        uint32_t n_parts, const uvhttp_tls_send_t* sends,
+                                        uint32_t n_sends, const uvhttp_tls_key_t* keys,
+                                        uint32_t n_keys, uint32_t max_fragment,
+                                        uvhttp_tls_seal_t* records, uint32_t max_records,
+                                        uvhttp_tls_send_result_t* results,
+                                        uvhttp_tls_send_summary_t* summary, uint8_t* out,
+                                        uint64_t out_cap, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,12 @@ the baseline, the two copies).  The record counts and bytes of the two are compa
 control_replies_streams after one decode_streams (tools/bench_replies.py's wire, 1 % PINGs; 1 % of
 the results marked failed on the host before the timed calls).
 
-    python tools/bench_parts.py [--steps K] [--warmup W] [--shapes c4,c3] [--scale S] [--close] [--out FILE]
+--coalesce times, per shape and for AES-128-GCM and ChaCha20-Poly1305 keys, uvhttp_tls_gpu_seal_parts_coalesced
+beside the same-run seal_parts over the same arena (the two alternate inside every step), with the
+records and output bytes of each and the coalesced call's time outside its seal kernels.
+
+    python tools/bench_parts.py [--steps K] [--warmup W] [--shapes c4,c3] [--scale S] [--close] [--coalesce]
+                                [--out FILE]
 
 One JSON line per shape on stdout (and appended to FILE), then nothing else.
 """
@@ -68,7 +73,9 @@ def table(sizes_per_conn):
     return off, np.stack([first, counts], 1).astype(np.uint32)
 
 
-def seal_shape(t, U, name, conns, steps, warmup):
+def workload(t, name, conns, cipher=0):
+    """the send arena of `conns` connections, its three frame tables and run tables, one TLS 1.3 key
+    per connection (cipher 0 = AES-128-GCM, 1 = ChaCha20-Poly1305) and the sends, on the device"""
     dev = "cuda:0"
     per, plen = SHAPES[name]
     rng = np.random.default_rng(0x5EED)
@@ -85,12 +92,25 @@ def seal_shape(t, U, name, conns, steps, warmup):
     d_runs = [up(runs) for _, runs in tabs]
     keys = np.zeros(conns, KEY_DT)
     keys["key"], keys["iv"] = rng.integers(0, 256, (conns, 32)), rng.integers(0, 256, (conns, 12))
-    keys["key_len"], keys["version"], keys["cipher"] = 16, 0x0304, 0
+    keys["key_len"], keys["version"], keys["cipher"] = 32 if cipher else 16, 0x0304, cipher
     d_keys = up(keys)
     sends = np.zeros(conns, SEND_DT)
     sends["seq"], sends["key"], sends["type"] = rng.integers(0, 1 << 40, conns), np.arange(conns), 23
     d_sends = up(sends)
     n_frames = [len(off) - 1 for off, _ in tabs]
+    parts = [(bases[k], lens[k], d_off[k], d_runs[k], 8, n_frames[k]) for k in range(3)]
+    return dict(hdr=hdr, plen=plen, echo=echo, pongs=pongs, closes=closes, tabs=tabs, lens=lens, bases=bases,
+                arena=arena, up=up, d_off=d_off, d_keys=d_keys, sends=sends, d_sends=d_sends, n_frames=n_frames,
+                parts=parts)
+
+
+def seal_shape(t, U, name, conns, steps, warmup):
+    dev = "cuda:0"
+    w = workload(t, name, conns)
+    hdr, plen, echo, pongs, closes, tabs, lens, bases = (w[k] for k in ("hdr", "plen", "echo", "pongs", "closes", "tabs",
+                                                                        "lens", "bases"))
+    arena, up, d_off, d_keys, sends, d_sends, n_frames, parts = (w[k] for k in ("arena", "up", "d_off", "d_keys", "sends",
+                                                                                "d_sends", "n_frames", "parts"))
     records = [int(sum(-(-int(s) // 16384) for x in part for s in x)) for part in (echo, pongs, closes)]
     over = 5 + 1 + 16
     out_bytes = [ln + r * over for ln, r in zip(lens, records)]
@@ -100,7 +120,6 @@ def seal_shape(t, U, name, conns, steps, warmup):
     recs = t.zeros((sum(records) + 1) * 32, dtype=t.uint8, device=dev)
     res = t.zeros(conns * 48, dtype=t.uint8, device=dev)
     summ = t.zeros(32, dtype=t.uint8, device=dev)
-    parts = [(bases[k], lens[k], d_off[k], d_runs[k], 8, n_frames[k]) for k in range(3)]
 
     def one():
         eng.seal_parts(arena, parts, d_sends, conns, d_keys, conns, sum(records), out, records=recs, results=res,
@@ -150,6 +169,72 @@ def seal_shape(t, U, name, conns, steps, warmup):
         "parts": rows["parts"], "same_run_three_calls": rows["three_calls"],
         "vs_three_calls": round(rows["parts"]["ms"] / rows["three_calls"]["ms"], 3),
         "gb_per_s": round(sum(lens) / rows["parts"]["ms"] / 1e6, 2),
+    }
+
+
+def coalesce_shape(t, U, name, conns, steps, warmup, cipher):
+    """uvhttp_tls_gpu_seal_parts_coalesced beside the same-run seal_parts over the same arena, the
+    two calls alternating inside every step, each bracketed by HIP events of its own; then each call
+    alone for the engine's own HIP-event time of the seal kernels (`crypto_ms`): what is left of a
+    coalesced call (`gather_plan_ms`) is its gather and its plan kernels."""
+    dev = "cuda:0"
+    w = workload(t, name, conns, cipher)
+    lens, arena, parts, d_sends, d_keys = w["lens"], w["arena"], w["parts"], w["d_sends"], w["d_keys"]
+    over = 5 + 1 + 16
+    per_frame = int(sum(-(-int(s) // 16384) for part in (w["echo"], w["pongs"], w["closes"]) for x in part for s in x))
+    stream = [int(sum(int(x[c].sum()) for x in (w["echo"], w["pongs"], w["closes"]))) for c in range(conns)]
+    packed = sum(-(-b // 16384) for b in stream)
+    need = {"parts": (per_frame, sum(lens) + per_frame * over), "coalesced": (packed, sum(lens) + packed * over)}
+    eng = U.TlsEngine(0)
+    eng.set_timing(True)
+    buf = {k: (t.zeros(b + 64, dtype=t.uint8, device=dev), t.zeros((r + 1) * 32, dtype=t.uint8, device=dev),
+               t.zeros(conns * 48, dtype=t.uint8, device=dev), t.zeros(32, dtype=t.uint8, device=dev))
+           for k, (r, b) in need.items()}
+    call = {"parts": eng.seal_parts, "coalesced": eng.seal_parts_coalesced}
+
+    def run(k):
+        out, recs, res, summ = buf[k]
+        call[k](arena, parts, d_sends, conns, d_keys, conns, need[k][0], out, records=recs, results=res, summary=summ)
+
+    for _ in range(warmup):
+        run("parts")
+        run("coalesced")
+    t.cuda.synchronize()
+    ev = [[t.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(steps)]
+    for a, b, c in ev:
+        a.record()
+        run("parts")
+        b.record()
+        run("coalesced")
+        c.record()
+    t.cuda.synchronize()
+    ms = {"parts": sorted(a.elapsed_time(b) for a, b, _ in ev), "coalesced": sorted(b.elapsed_time(c) for _, b, c in ev)}
+    rows = {}
+    for k in ("parts", "coalesced"):
+        eng.kernel_time()
+        for _ in range(steps):
+            run(k)
+        t.cuda.synchronize()
+        crypto, _ = eng.kernel_time()
+        summ = np.frombuffer(buf[k][3].cpu().numpy().tobytes(), "<u8")
+        assert (int(summ[1] & 0xFFFFFFFF), int(summ[0]), int(summ[1] >> 32)) == (*need[k], 0), (k, summ, need[k])
+        med = ms[k][len(ms[k]) // 2]
+        rows[k] = {"ms": round(med, 4), "min_ms": round(ms[k][0], 4), "mean_ms": round(sum(ms[k]) / steps, 4),
+                   "crypto_ms": round(crypto / steps, 4), "records": need[k][0], "out_bytes": need[k][1]}
+    rows["coalesced"]["gather_plan_ms"] = round(rows["coalesced"]["ms"] - rows["coalesced"]["crypto_ms"], 4)
+    rows["coalesced"]["gather_plan_share"] = round(rows["coalesced"]["gather_plan_ms"] / rows["coalesced"]["ms"], 3)
+    # the same sequence numbers' worth of plaintext: plain_len per send is equal
+    assert t.equal(buf["parts"][2].view(t.int64).view(conns, 6)[:, 5], buf["coalesced"][2].view(t.int64).view(conns, 6)[:, 5])
+    eng.close()
+    return {
+        "metric": "seal_parts_coalesced over three parts, ms per call (device-resident)",
+        "value": rows["coalesced"]["ms"], "unit": "ms", "n_gpus": 1, "higher_is_better": False, "steps": steps,
+        "warmup": warmup, "shape": name, "aead": "chacha20-poly1305" if cipher else "aes-128-gcm",
+        "config": {"connections": conns, "echoes": w["n_frames"][0], "echo_frame_bytes": w["hdr"] + w["plen"],
+                   "replies": w["n_frames"][1], "closes": w["n_frames"][2], "frame_bytes": sum(lens)},
+        "coalesced": rows["coalesced"], "same_run_seal_parts": rows["parts"],
+        "vs_seal_parts": round(rows["coalesced"]["ms"] / rows["parts"]["ms"], 3),
+        "gb_per_s": round(sum(lens) / rows["coalesced"]["ms"] / 1e6, 2),
     }
 
 
@@ -210,13 +295,20 @@ def main():
     ap.add_argument("--shapes", default="c4,c3")
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the 4 096 connections (smoke runs)")
     ap.add_argument("--close", action="store_true", help="also time the close pass beside the control replies")
+    ap.add_argument("--coalesce", action="store_true",
+                    help="time seal_parts_coalesced beside seal_parts, both AEADs, instead of the shapes' default rows")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     args = ap.parse_args()
 
     import torch
     import uvhttp_amd as U
     conns = max(1, int(4096 * args.scale))
-    lines = [seal_shape(torch, U, name, conns, args.steps, args.warmup) for name in args.shapes.split(",") if name]
+    names = [name for name in args.shapes.split(",") if name]
+    if args.coalesce:
+        lines = [coalesce_shape(torch, U, name, conns, args.steps, args.warmup, cipher) for name in names
+                 for cipher in (0, 1)]
+    else:
+        lines = [seal_shape(torch, U, name, conns, args.steps, args.warmup) for name in names]
     if args.close:
         lines.append(close_pass(torch, U, conns, args.steps, args.warmup))
     for line in lines:

@@ -582,6 +582,8 @@ def load_library(path: str) -> C.CDLL:
                                                  u32, vp, vp, vp, u64, vp]),
         "uvhttp_tls_gpu_seal_parts": (C.c_int, [vp, vp, u64, C.POINTER(TlsPart), u32, vp, u32, vp, u32,
                                                 u32, vp, u32, vp, vp, vp, u64, vp]),
+        "uvhttp_tls_gpu_seal_parts_coalesced": (C.c_int, [vp, vp, u64, C.POINTER(TlsPart), u32, vp, u32, vp,
+                                                          u32, u32, vp, u32, vp, vp, vp, u64, vp]),
         "uvhttp_tls_gpu_ws_streams": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
@@ -1728,6 +1730,21 @@ class TlsEngine:
         TlsPart or of (base, len, frame_off tensor, runs tensor, run_stride, n_frames) tuples, sends
         a device tensor of uvhttp_tls_send_t (seq, key, type) -> (records, results, summary) device
         tensors, as seal_frames."""
+        return self._seal_parts("seal_parts", frames, parts, sends, n_sends, keys, n_keys, max_records, out,
+                                max_fragment, records, results, summary, frames_len, stream)
+
+    def seal_parts_coalesced(self, frames, parts, sends, n_sends, keys, n_keys, max_records, out,
+                             max_fragment=0, records=None, results=None, summary=None, frames_len=None,
+                             stream=None):
+        """uvhttp_tls_gpu_seal_parts_coalesced: seal_parts' arguments and returns; every send's frames
+        are packed into ceil(bytes / max_fragment) full records instead of being cut frame by frame.
+        records[r].src_off points into `out` (where the content was gathered and sealed in place);
+        `out` may not overlap `frames`."""
+        return self._seal_parts("seal_parts_coalesced", frames, parts, sends, n_sends, keys, n_keys,
+                                max_records, out, max_fragment, records, results, summary, frames_len, stream)
+
+    def _seal_parts(self, name, frames, parts, sends, n_sends, keys, n_keys, max_records, out, max_fragment,
+                    records, results, summary, frames_len, stream):
         t = self.torch
         dev = f"cuda:{self.device}"
         if records is None:
@@ -1745,10 +1762,10 @@ class TlsEngine:
                 tab[k] = TlsPart(base, ln, off.data_ptr() if hasattr(off, "data_ptr") else off,
                                  runs.data_ptr() if hasattr(runs, "data_ptr") else runs, stride, n)
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
-        self._check(self._L.uvhttp_tls_gpu_seal_parts(
+        self._check(getattr(self._L, "uvhttp_tls_gpu_" + name)(
             self.h, ptr(frames), frames.numel() if frames_len is None else frames_len, tab, len(parts),
             ptr(sends), n_sends, ptr(keys), n_keys, max_fragment, ptr(records), max_records,
-            ptr(results), ptr(summary), ptr(out), out.numel(), self._stream(stream)), "seal_parts")
+            ptr(results), ptr(summary), ptr(out), out.numel(), self._stream(stream)), name)
         return records, results, summary
 
 

@@ -2642,6 +2642,225 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_fill(PartsArgs a) {
     }
 }
 
+// ---- send side, a send's frames coalesced into full records (uvhttp_tls_gpu_seal_parts_coalesced) --
+//
+// A send's stream is its parts' runs back to back; a run without a bad frame is one contiguous
+// range of the arena, so the stream has at most 8 segments whatever the number of frames.  The
+// frame launches above give fr_bad (their record counts are not used), k_tls_coal_count makes a
+// send's segment table and its record and byte counts from at most 8 offset differences,
+// k_tls_send_scan / k_tls_send_write lay the sends out as they stand, k_tls_coal_fill writes a
+// record from closed-form arithmetic, k_tls_coal_gather copies every record's content to where its
+// ciphertext will lie (out + out_off + header), and the seal kernels run over records[] with
+// src = out, in place.
+
+struct CoalSeg {        // segment p of a send's stream
+    uint64_t src;       // its first byte in frames
+    uint64_t end;       // stream bytes up to and including it (entries past n_parts: the total)
+};
+
+struct CoalRec {        // fill -> gather, per record
+    uint64_t pos;       // stream position of the record's first content byte
+    uint32_t send;
+    uint32_t reserved;
+};
+
+struct CoalArgs {
+    PartsArgs p;
+    CoalSeg* seg;       // [n_sends][UVHTTP_TLS_MAX_PARTS]
+    CoalRec* crec;      // [max_records]
+};
+
+constexpr uint32_t kGatherTile = 4096;  // record content bytes per workgroup pass: 16 per lane
+
+__global__ __launch_bounds__(kBlock) void k_tls_coal_count(CoalArgs c) {
+    const PartsArgs& a = c.p;
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    uint64_t n_rec = 0, bytes = 0, failed = 0;
+    if (s < a.n_sends) {
+        const uvhttp_tls_send_t sd = a.sends[s];
+        CoalSeg* sg = c.seg + (uint64_t)UVHTTP_TLS_MAX_PARTS * s;
+        int32_t st = 0;
+        uint32_t over = 0;
+        if (sd.key >= a.n_keys || sd.key > 0xFFFFu || a.sched[sd.key].nr == 0) {
+            st = UVHTTP_TLS_REC_ERR_KEY;
+        } else {
+            uint64_t plain = 0;
+            for (uint32_t p = 0; p < a.n_parts; ++p) {
+                const uvhttp_tls_part_t& q = a.part[p];
+                uint32_t first, n;
+                parts_run(q, s, &first, &n);
+                const uint64_t last = (uint64_t)first + n;
+                const uint64_t fb = a.fbase[p];
+                if (last > q.n_frames || a.fr_bad[fb + last] != a.fr_bad[fb + first]) {
+                    st = UVHTTP_TLS_REC_ERR_RANGE;
+                    break;
+                }
+                // (no bad frame in the run: its offsets do not decrease and end within q.len)
+                uint64_t src = 0;
+                if (n) {
+                    const uint64_t b = q.frame_off[first];
+                    src = q.base + b;
+                    plain += q.frame_off[last] - b;
+                }
+                sg[p] = CoalSeg{src, plain};
+            }
+            if (!st) {
+                for (uint32_t p = a.n_parts; p < UVHTTP_TLS_MAX_PARTS; ++p) sg[p] = CoalSeg{0, plain};
+                const KeySched* k = a.sched + sd.key;
+                over = 5 + 16 + explicit_len(k->version, k->cipher) +
+                       (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
+                n_rec = (plain + a.max_fragment - 1) / a.max_fragment;
+                bytes = plain + n_rec * over;
+            }
+        }
+        failed = st ? 1 : 0;
+        a.sw[s] = SendWork{n_rec, bytes, st, over};
+    }
+    uint64_t tn, tb, tf;
+    (void)block_exclusive_sum<uint64_t>(n_rec, &tn);
+    (void)block_exclusive_sum<uint64_t>(bytes, &tb);
+    (void)block_exclusive_sum<uint64_t>(failed, &tf);
+    if (threadIdx.x == 0) {
+        a.sblk[3 * blockIdx.x] = tn;
+        a.sblk[3 * blockIdx.x + 1] = tb;
+        a.sblk[3 * blockIdx.x + 2] = tf;
+    }
+}
+
+// one lane per record: its send (the last one whose first_record <= r); the rest is arithmetic,
+// every record of a send but the last holding max_fragment bytes
+__global__ __launch_bounds__(kBlock) void k_tls_coal_fill(CoalArgs c) {
+    const PartsArgs& a = c.p;
+    const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
+    for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
+        uint32_t lo = 0, hi = a.n_sends;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.s_first[mid] <= r) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t s = lo;
+        const uvhttp_tls_send_t sd = a.sends[s];
+        const SendWork sw = a.sw[s];
+        const KeySched* ks = a.sched + sd.key;
+        const uint64_t k = r - a.s_first[s];
+        const uint64_t pos = k * a.max_fragment;
+        const uint64_t left = sw.bytes - sw.n_rec * sw.over - pos;
+        uvhttp_tls_seal_t o;
+        o.out_off = a.s_out[s] + k * (a.max_fragment + sw.over);
+        o.src_off = o.out_off + 5 + explicit_len(ks->version, ks->cipher);
+        o.seq = sd.seq + k;
+        o.plain_len = left < a.max_fragment ? (uint32_t)left : a.max_fragment;
+        o.key = (uint16_t)sd.key;
+        o.type = sd.type;
+        o.reserved = 0;
+        a.records[r] = o;
+        c.crec[r] = CoalRec{pos, s, 0};
+    }
+}
+
+struct GatherArgs {
+    const uint8_t* frames;
+    uint64_t frames_len;
+    uint8_t* out;
+    const uvhttp_tls_seal_t* records;
+    uint32_t max_records;
+    uint32_t tiles_per_rec;  // ceil(max_fragment / kGatherTile)
+    const CoalSeg* seg;
+    const CoalRec* crec;
+    const uint32_t* n_total;
+};
+
+// where stream byte `pos` of a send lies in frames, and how many stream bytes from it on are
+// contiguous there (pos < the stream's length)
+__device__ inline uint64_t coal_locate(const CoalSeg (&sg)[UVHTTP_TLS_MAX_PARTS], uint64_t pos, uint64_t* run) {
+    uint64_t beg = 0, src = 0, n = 0;
+    bool found = false;
+#pragma unroll
+    for (int p = 0; p < UVHTTP_TLS_MAX_PARTS; ++p) {
+        const bool here = !found && pos < sg[p].end;
+        if (here) {
+            src = sg[p].src + (pos - beg);
+            n = sg[p].end - pos;
+            found = true;
+        }
+        beg = sg[p].end;
+    }
+    *run = n;
+    return src;
+}
+
+// frames[o, o + 16), all 16 inside the buffer: away from its ends, the two aligned 16-byte vectors
+// around them and a byte funnel shift (an unaligned 16-byte copy compiles to byte loads on gfx950)
+__device__ inline uint4 coal_load16(const uint8_t* frames, uint64_t frames_len, uint64_t o) {
+    const uintptr_t base = reinterpret_cast<uintptr_t>(frames), a = base + o;
+    const uintptr_t lo = a & ~(uintptr_t)15;
+    if (lo >= base && lo + 32 <= base + frames_len) {
+        const uint8_t* al16 = static_cast<const uint8_t*>(__builtin_assume_aligned(frames + (lo - base), 16));
+        const uint4 v0 = *reinterpret_cast<const uint4*>(al16);
+        const uint4 v1 = *reinterpret_cast<const uint4*>(al16 + 16);
+        uint64_t x0 = v0.x | ((uint64_t)v0.y << 32), x1 = v0.z | ((uint64_t)v0.w << 32);
+        uint64_t x2 = v1.x | ((uint64_t)v1.y << 32);
+        const uint64_t x3 = v1.z | ((uint64_t)v1.w << 32);
+        const uint32_t d = (uint32_t)(a & 15);
+        if (d & 8) {
+            x0 = x1;
+            x1 = x2;
+            x2 = x3;
+        }
+        const uint32_t sh = (d & 7) * 8;
+        const uint64_t r0 = sh ? (x0 >> sh) | (x1 << (64 - sh)) : x0;
+        const uint64_t r1 = sh ? (x1 >> sh) | (x2 << (64 - sh)) : x1;
+        return uint4{(uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32)};
+    }
+    uint32_t t[4] = {0, 0, 0, 0};
+    for (uint32_t k = 0; k < 16; ++k) t[k >> 2] |= (uint32_t)frames[o + k] << (8 * (k & 3));
+    return uint4{t[0], t[1], t[2], t[3]};
+}
+
+// One workgroup per tile of kGatherTile content bytes of one record; a lane per 16-byte vector of
+// out at an aligned address.  A vector wholly inside the tile whose 16 stream bytes lie in one
+// segment is one funnelled fetch and one aligned 16-byte store; the vectors on the tile's edges
+// (which are the record's edges, or the neighbouring tile's bytes) and those a segment boundary
+// crosses go byte by byte, so no store touches a byte outside [lo, hi) of the record's content.
+__global__ __launch_bounds__(kBlock) void k_tls_coal_gather(GatherArgs g) {
+    const uint32_t n = g.n_total[0] < g.max_records ? g.n_total[0] : g.max_records;
+    const uint64_t items = (uint64_t)n * g.tiles_per_rec;
+    for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const uint32_t r = (uint32_t)(w / g.tiles_per_rec);
+        const uint32_t lo = (uint32_t)(w % g.tiles_per_rec) * kGatherTile;
+        const uvhttp_tls_seal_t sr = g.records[r];
+        if (lo >= sr.plain_len) continue;
+        const uint32_t hi = lo + kGatherTile < sr.plain_len ? lo + kGatherTile : sr.plain_len;
+        const CoalRec cr = g.crec[r];
+        CoalSeg sg[UVHTTP_TLS_MAX_PARTS];
+#pragma unroll
+        for (int p = 0; p < UVHTTP_TLS_MAX_PARTS; ++p) sg[p] = g.seg[(uint64_t)UVHTTP_TLS_MAX_PARTS * cr.send + p];
+        uint8_t* content = g.out + sr.src_off;
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(content);
+        const uintptr_t d_lo = c0 + lo, d_hi = c0 + hi;
+        const uintptr_t a0 = d_lo & ~(uintptr_t)15;
+        const uint32_t n_vec = (uint32_t)((d_hi - a0 + 15) / 16);
+        for (uint32_t v = threadIdx.x; v < n_vec; v += kBlock) {
+            const uintptr_t va = a0 + 16 * (uintptr_t)v;
+            const uintptr_t b = va > d_lo ? va : d_lo, e = va + 16 < d_hi ? va + 16 : d_hi;
+            const uint64_t pos = cr.pos + (b - c0);
+            uint64_t run;
+            const uint64_t src = coal_locate(sg, pos, &run);
+            if (e - b == 16 && run >= 16) {
+                uint8_t* dst = static_cast<uint8_t*>(__builtin_assume_aligned(content + (va - c0), 16));
+                *reinterpret_cast<uint4*>(dst) = coal_load16(g.frames, g.frames_len, src);
+            } else {
+                for (uint32_t i = 0; i < (uint32_t)(e - b); ++i) {
+                    uint64_t one;
+                    const uint64_t at = i < run ? src + i : coal_locate(sg, pos + i, &one);
+                    content[b - c0 + i] = g.frames[at];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---- engine ---------------------------------------------------------------------------------
@@ -2666,6 +2885,9 @@ struct uvhttp_tls_gpu_engine {
     uint64_t* sblk;
     uint32_t* s_first;
     uint64_t* s_out;
+    uint32_t cap_csends, cap_crecs;  // seal_parts_coalesced: segment tables, per-record places
+    CoalSeg* coal_seg;
+    CoalRec* coal_rec;
     int timing;
     hipEvent_t ev[2 * 256];
     int ev_created, ev_used;
@@ -2696,15 +2918,18 @@ static int tls_err(uvhttp_tls_gpu_engine_t* e, int code, const char* what, hipEr
 static size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t streams, uint32_t records,
-                       uint32_t frames = 0, uint32_t sends = 0) {
+                       uint32_t frames = 0, uint32_t sends = 0, uint32_t csends = 0, uint32_t crecs = 0) {
     if (e->ws && keys <= e->cap_keys && streams <= e->cap_streams && records <= e->cap_records &&
-        frames <= e->cap_frames && sends <= e->cap_sends)
+        frames <= e->cap_frames && sends <= e->cap_sends && csends <= e->cap_csends &&
+        crecs <= e->cap_crecs)
         return UVHTTP_TLS_GPU_OK;
     keys = keys > e->cap_keys ? keys : e->cap_keys;
     streams = streams > e->cap_streams ? streams : e->cap_streams;
     records = records > e->cap_records ? records : e->cap_records;
     frames = frames > e->cap_frames ? frames : e->cap_frames;
     sends = sends > e->cap_sends ? sends : e->cap_sends;
+    csends = csends > e->cap_csends ? csends : e->cap_csends;
+    crecs = crecs > e->cap_crecs ? crecs : e->cap_crecs;
     const size_t nblk = (streams + kBlock - 1) / kBlock + 1;
     const size_t o_sched = 0;
     const size_t o_work = al(o_sched + (size_t)(keys ? keys : 1) * sizeof(KeySched));
@@ -2720,12 +2945,15 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
     const size_t o_sblk = al(o_sw2 + (size_t)(sends ? sends : 1) * sizeof(SendWork));
     const size_t o_sfirst = al(o_sblk + 3 * nsblk * sizeof(uint64_t));
     const size_t o_sout = al(o_sfirst + (size_t)(sends ? sends : 1) * sizeof(uint32_t));
-    const size_t bytes = al(o_sout + (size_t)(sends ? sends : 1) * sizeof(uint64_t));
+    const size_t o_cseg = al(o_sout + (size_t)(sends ? sends : 1) * sizeof(uint64_t));
+    const size_t o_crec = al(o_cseg + (size_t)csends * UVHTTP_TLS_MAX_PARTS * sizeof(CoalSeg));
+    const size_t bytes = al(o_crec + (size_t)crecs * sizeof(CoalRec)) + 256;
     if (e->ws) (void)hipFree(e->ws);
     e->ws = nullptr;
     const hipError_t h = hipMalloc(&e->ws, bytes);
     if (h != hipSuccess) {
         e->cap_keys = e->cap_streams = e->cap_records = e->cap_frames = e->cap_sends = 0;
+        e->cap_csends = e->cap_crecs = 0;
         return tls_err(e, UVHTTP_TLS_GPU_ENOMEM, "hipMalloc tls workspace", h);
     }
     char* b = (char*)e->ws;
@@ -2736,6 +2964,7 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
         (void)hipFree(e->ws);
         e->ws = nullptr;
         e->cap_keys = e->cap_streams = e->cap_records = e->cap_frames = e->cap_sends = 0;
+        e->cap_csends = e->cap_crecs = 0;
         return tls_err(e, UVHTTP_TLS_GPU_ENOMEM, "hipMemset tls key slots", hz);
     }
     e->work = (RecWork*)(b + o_work);
@@ -2750,12 +2979,16 @@ static int tls_reserve(uvhttp_tls_gpu_engine_t* e, uint32_t keys, uint32_t strea
     e->sblk = (uint64_t*)(b + o_sblk);
     e->s_first = (uint32_t*)(b + o_sfirst);
     e->s_out = (uint64_t*)(b + o_sout);
+    e->coal_seg = (CoalSeg*)(b + o_cseg);
+    e->coal_rec = (CoalRec*)(b + o_crec);
     e->ws_bytes = bytes;
     e->cap_keys = keys;
     e->cap_streams = streams;
     e->cap_records = records;
     e->cap_frames = frames;
     e->cap_sends = sends;
+    e->cap_csends = csends;
+    e->cap_crecs = crecs;
     return UVHTTP_TLS_GPU_OK;
 }
 
@@ -3130,6 +3363,127 @@ int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames,
         // the seal kernels read their count from n_total[0]; grids from max_records, capped
         SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
                    e->n_total};
+        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
+        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
+        const int tk = tls_timing_begin(e, s);
+        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
+        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
+        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
+        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
+        tls_timing_end(e, tk, s);
+    }
+    const hipError_t h = hipGetLastError();
+    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
+    return UVHTTP_TLS_GPU_OK;
+}
+
+int uvhttp_tls_gpu_seal_parts_coalesced(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames,
+                                        uint64_t frames_len, const uvhttp_tls_part_t* parts,
+                                        uint32_t n_parts, const uvhttp_tls_send_t* sends,
+                                        uint32_t n_sends, const uvhttp_tls_key_t* keys, uint32_t n_keys,
+                                        uint32_t max_fragment, uvhttp_tls_seal_t* records,
+                                        uint32_t max_records, uvhttp_tls_send_result_t* results,
+                                        uvhttp_tls_send_summary_t* summary, uint8_t* out,
+                                        uint64_t out_cap, void* stream) {
+    if (!e) {  // no engine: there is none without a device
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
+        return UVHTTP_TLS_GPU_EINVAL;
+    }
+    if (!parts || n_parts == 0 || n_parts > UVHTTP_TLS_MAX_PARTS || (!frames && frames_len) ||
+        (!sends && n_sends) || (!keys && n_keys) || (!records && max_records) || (!results && n_sends) ||
+        !summary || (!out && out_cap) || max_fragment > 16384)
+        return UVHTTP_TLS_GPU_EINVAL;
+    if (n_sends > (1u << 26) || max_records > (1u << 28))
+        return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / records", hipSuccess);
+    // the content is gathered into out and sealed there: out may not hold any of the frames
+    if (frames_len && out_cap && (uintptr_t)out < (uintptr_t)frames + frames_len &&
+        (uintptr_t)frames < (uintptr_t)out + out_cap)
+        return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts_coalesced: out overlaps frames", hipSuccess);
+    CoalArgs c;
+    memset(&c, 0, sizeof(c));
+    PartsArgs& p = c.p;
+    uint64_t n_frames_all = 0;
+    for (uint32_t k = 0; k < n_parts; ++k) {
+        const uvhttp_tls_part_t& q = parts[k];
+        if (!q.frame_off || !q.runs || ((uintptr_t)q.frame_off & 7u) || ((uintptr_t)q.runs & 3u) ||
+            q.run_stride < 8 || (q.run_stride & 3u) || q.base > frames_len || q.len > frames_len - q.base)
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts_coalesced: a part's pointers, stride or range",
+                           hipSuccess);
+        n_frames_all += q.n_frames;
+        if (n_frames_all > (1u << 28))
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many frames", hipSuccess);
+        p.part[k] = q;
+        p.fbase[k + 1] = p.fbase[k] + q.n_frames + 1;
+        p.bbase[k + 1] = p.bbase[k] + (q.n_frames + 1 + kBlock - 1) / kBlock;
+    }
+    DeviceGuard dev(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (!n_sends) {
+        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
+        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
+        return UVHTTP_TLS_GPU_OK;
+    }
+    // the frame scratch as in seal_parts; 8 x 16 bytes of segment table per send, 16 per record
+    int rc = tls_reserve(e, n_keys, 1, 1, p.fbase[n_parts] + UVHTTP_TLS_MAX_PARTS * kBlock, n_sends, n_sends,
+                         max_records);
+    if (rc) return rc;
+    tls_call_begin(e, s);
+    if (n_keys)
+        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
+    p.n_parts = n_parts;
+    p.max_fragment = max_fragment ? max_fragment : 16384u;
+    p.sends = sends;
+    p.n_sends = n_sends;
+    p.n_keys = n_keys;
+    p.sched = e->sched;
+    p.records = records;
+    p.max_records = max_records;
+    p.fr_rec = e->fr_rec;
+    p.fr_bad = e->fr_bad;
+    p.fblk = e->fblk;
+    p.sw = e->send_work;
+    p.sblk = e->sblk;
+    p.s_first = e->s_first;
+    p.s_out = e->s_out;
+    p.n_total = e->n_total;
+    c.seg = e->coal_seg;
+    c.crec = e->coal_rec;
+    SendArgs q;  // what k_tls_send_scan / k_tls_send_write read
+    memset(&q, 0, sizeof(q));
+    q.sends = sends;
+    q.n_sends = n_sends;
+    q.max_records = max_records;
+    q.results = results;
+    q.summary = summary;
+    q.out_cap = out_cap;
+    q.sw = e->send_work;
+    q.sblk = e->sblk;
+    q.s_first = e->s_first;
+    q.s_out = e->s_out;
+    q.n_total = e->n_total;
+    const uint32_t nfb = p.bbase[n_parts];
+    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_tls_parts_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_scan, dim3(n_parts), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_coal_count, dim3(nsb), dim3(kBlock), 0, s, c);
+    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, q, nsb);
+    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, q);
+    if (max_records) {
+        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
+        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
+        hipLaunchKernelGGL(k_tls_coal_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, c);
+        // the gather and the seal kernels read their count from n_total[0] (0 on a capacity
+        // failure: nothing is gathered either); grids from max_records, capped
+        GatherArgs g{frames, frames_len, out, records, max_records,
+                     (p.max_fragment + kGatherTile - 1) / kGatherTile, e->coal_seg, e->coal_rec, e->n_total};
+        const uint64_t need_g = (uint64_t)max_records * g.tiles_per_rec;
+        const uint64_t cap_g = (uint64_t)e->crypt_grid * 8;
+        hipLaunchKernelGGL(k_tls_coal_gather, dim3((uint32_t)(need_g < cap_g ? need_g : cap_g)), dim3(kBlock), 0, s, g);
+        // in place: a record's content lies at out + src_off = out + out_off + header
+        SealArgs a{out, out_cap, records, max_records, out, out_cap, e->sched, n_keys, e->te0, e->n_total};
         const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
         const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
         const int tk = tls_timing_begin(e, s);
