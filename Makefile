@@ -108,7 +108,7 @@ oracle:
 
 # test programs: the C1 libuv echo harness (against the product library) and the
 # ASan/UBSan builds of the host decoder + oracle (tests/c/Makefile)
-ctests: $(LIB) oracle tests/c/_build/close_check tests/c/_build/fail_check
+ctests: $(LIB) oracle tests/c/_build/close_check tests/c/_build/fail_check tests/c/_build/answer_check
 	$(MAKE) -C tests/c
 
 # the server's own CLOSE frames (ws_host.c: uvhttp_ws_close_frames) under ASan/UBSan, in a program
@@ -124,6 +124,13 @@ tests/c/_build/fail_check: tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c includ
 	@mkdir -p tests/c/_build
 	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
 	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c
+
+# the answers (ws_host.c: uvhttp_ws_answer_messages) under ASan/UBSan, likewise
+# (tests/c/answer_check.c, run by tests/test_answer_host.py)
+tests/c/_build/answer_check: tests/c/answer_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
+	@mkdir -p tests/c/_build
+	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
+	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/answer_check.c uvhttp_amd/csrc/ws_host.c
 
 # measurement tools run on the GPU box (PCIe ceilings beside the live-shape e2e)
 probes: tools/bin/pcie_probe tools/bin/copy_probe

@@ -919,7 +919,9 @@ int uvhttp_ws_control_replies(const uint8_t* wire, uint64_t wire_len,
  *
  * Order on one connection.  The reference interleaves echoes and control replies in frame order;
  * echo_messages and control_replies give two runs.  A caller who seals both sends a connection's
- * echo run before its control-reply run, so that a CLOSE echo stays last.
+ * echo run before its control-reply run, so that a CLOSE echo stays last.  For the reference's
+ * own order — one run, every answer where its frame stood — use
+ * uvhttp_ws_gpu_answer_messages_streams / _inplace (below).
  *
  * All pointers are device pointers: d_wire, d_out, d_open and d_carry 16-byte aligned, d_desc,
  * d_streams, d_results, d_batch_summary, d_out_off, d_carry_off, d_open_off, d_conn and
@@ -998,6 +1000,122 @@ int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
                             uint8_t* out, uint64_t out_cap, uint64_t* out_off,
                             uint32_t max_echoes, uint8_t* open, uint64_t open_cap,
                             uvhttp_ws_echo_conn_t* conn_result);
+
+/* ---- answers: echoes and control replies of a batch in one run, in frame order -------------- */
+/* uvhttp_ws_process_data answers as it goes (src/uvhttp_websocket.c:1016-1084): a PING gets its
+ * PONG when it is processed, a message its echo when its FIN frame is, and the CLOSE echo comes
+ * where the CLOSE stood.  These calls build that one sequence for a whole decoded batch: a
+ * connection's run opens to exactly the bytes uvhttp_ws_send_frame would have been handed, in
+ * order.  They take echo_messages_streams' (_inplace's) arguments, argument for argument, with
+ * max_answers for max_echoes, the structs below for d_conn and d_summary, and one optional output,
+ * d_reply_conn.
+ *
+ * Rule, per connection.  Over the considered descriptors desc[first_frame, first_frame +
+ * n_delivered), clipped and skipped exactly as echo_messages does it, in descriptor order:
+ *   the FIN frame of an echoed message gives that message's echo frame: the bytes echo_messages
+ *     builds, with its membership, carry, after-first-CLOSE and SERVER_SEND rules;
+ *   a delivered PING gives a PONG and a delivered CLOSE its CLOSE echo: the bytes
+ *     control_replies builds (an empty CLOSE for payload_len < 2).  Nothing after the first
+ *     delivered CLOSE is answered unless UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE is set;
+ *   every other frame gives nothing.
+ * A connection's output is therefore the stable merge, by source descriptor index, of the two
+ * calls' outputs for it.  Echoes after the first CLOSE are never sent, whatever the flag; by
+ * default the CLOSE echo is the connection's last answer.
+ *
+ * Keys.  Answer slot j (its index in this call's output) of a client connection takes
+ * d_mask_keys[j] (max_answers entries; NULL only when every enabled stream is a server).
+ *
+ * Statuses are the echo's values, checked in this order: NO_KEYS, NO_CARRY, BAD_RANGE — a
+ * delivered data frame, or a delivered PING or CLOSE whether answered or not, whose payload range
+ * (for a control frame: the reply's payload) lies outside [0, wire_len).  A connection with any of
+ * them gets no answers at all and open_len 0, and nothing outside the wire or the carry is read
+ * for it.  This is stricter than the two calls run apart: there NO_CARRY or a bad data range
+ * leaves the control replies standing, and a bad control range the echoes.
+ *
+ * Layout: the builders' convention.  Answers lie back to back in d_out, connections in index
+ * order; d_out_off has max_answers + 1 entries, the tail filled with the total; (first_answer,
+ * n_answers) goes to (char*)d_runs + s * run_stride; the open messages go to d_open / d_open_off
+ * as the next call's carry.  Capacity is the echo's rule: nothing is written, all offsets and runs
+ * are 0, every per-connection result is zero but for status ERR_CAPACITY, and the summary holds the
+ * totals needed (n_answers, n_replies, out_bytes, open_bytes, n_closed_conns).
+ *
+ * d_reply_conn (may be NULL) receives per connection what close_frames_streams reads, so that it
+ * runs after this call unchanged: closed as control_replies defines it (a CLOSE was delivered,
+ * answered or not, enabled or not, also on capacity), n_replies, out_len = the bytes of its replies
+ * (saturating), first_reply 0, and status REPLY_OK, or ERR_CAPACITY / BAD_RANGE / NO_KEYS when that
+ * is the connection's answer status (NO_CARRY reads REPLY_OK with no replies).
+ *
+ * The in-place form after decode_compact: data payloads lie in the arena and control payloads
+ * stay in the wire, and the call takes one d_wire.  Pass the arena only for a batch whose PINGs and
+ * CLOSEs carry no payload; otherwise use decode_inplace, or the two calls with a buffer each.
+ *
+ * EINVAL rules (and flags outside the two below), alignment (d_reply_conn 4), the stream rule and
+ * the graph-capture rule are echo_messages'.  Engine scratch is the echo's, sized by max_answers,
+ * plus 16 bytes per connection and 8 per 256 descriptors. */
+#define UVHTTP_WS_ANSWER_SERVER_SEND 0x1u        /* flags: UVHTTP_WS_ECHO_SERVER_SEND's rule */
+#define UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE 0x2u  /* flags: UVHTTP_WS_REPLY_AFTER_CLOSE's rule */
+
+typedef struct {            /* 32 B, one per connection, device-written */
+    uint32_t first_answer;  /* index of the connection's first answer in d_out_off */
+    uint32_t n_answers;
+    uint64_t out_len;       /* bytes of its answer frames */
+    uint64_t open_len;      /* bytes of the message still open after its last considered frame */
+    uint8_t status;         /* UVHTTP_WS_ECHO_* */
+    uint8_t open_opcode;    /* that message's opcode (0 when open_len is 0) */
+    uint8_t closed;         /* a CLOSE was delivered, whether answered or not */
+    uint8_t reserved;
+    uint32_t n_replies;     /* the PONGs and CLOSE echoes among its answers */
+} uvhttp_ws_answer_conn_t;
+
+typedef struct {            /* 32 B */
+    uint64_t out_bytes;     /* bytes of d_out the call needs */
+    uint64_t open_bytes;    /* bytes of d_open the call needs */
+    uint32_t n_answers;     /* answers the call needs */
+    uint32_t n_replies;     /* ... of which PONGs and CLOSE echoes */
+    uint32_t n_closed_conns;
+    int32_t status;         /* UVHTTP_WS_ECHO_OK or UVHTTP_WS_ECHO_ERR_CAPACITY */
+} uvhttp_ws_answer_summary_t;
+
+int uvhttp_ws_gpu_answer_messages_streams(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                          uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                          uint32_t max_frames, const uvhttp_ws_stream_t* d_streams,
+                                          const uvhttp_ws_stream_result_t* d_results,
+                                          uint32_t n_streams, const uint8_t* d_enable,
+                                          const uint32_t* d_mask_keys, uint32_t flags,
+                                          const uint8_t* d_carry, uint64_t carry_len,
+                                          const uint64_t* d_carry_off, uint8_t* d_out,
+                                          uint64_t out_cap, uint64_t* d_out_off, uint32_t max_answers,
+                                          uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open,
+                                          uint64_t open_cap, uint64_t* d_open_off,
+                                          uvhttp_ws_answer_conn_t* d_conn,
+                                          uvhttp_ws_answer_summary_t* d_summary,
+                                          uvhttp_ws_reply_conn_t* d_reply_conn, void* stream);
+int uvhttp_ws_gpu_answer_messages_inplace(uvhttp_ws_gpu_engine_t* eng, const uint8_t* d_wire,
+                                          uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+                                          uint32_t n_frames,
+                                          const uvhttp_ws_batch_summary_t* d_batch_summary,
+                                          int32_t is_server, const uint32_t* d_mask_keys,
+                                          uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                                          uint64_t* d_out_off, uint32_t max_answers, uint32_t* d_runs,
+                                          uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+                                          uint64_t* d_open_off, uvhttp_ws_answer_conn_t* d_conn,
+                                          uvhttp_ws_answer_summary_t* d_summary,
+                                          uvhttp_ws_reply_conn_t* d_reply_conn, void* stream);
+/* Host twin (plain C, host copies): one connection, first_answer 0, answer j takes mask_keys[j];
+ * the arguments are uvhttp_ws_echo_messages' with max_answers and the optional reply_conn.  The
+ * statement of the rule: "device == host" in every output.  On capacity nothing is written to out
+ * or open, out_off is all 0 and the result holds the needed n_answers, n_replies, out_len and
+ * open_len with status ERR_CAPACITY.  Returns 0, or -1 for the arguments uvhttp_ws_echo_messages
+ * refuses and for unknown flags. */
+int uvhttp_ws_answer_messages(const uint8_t* wire, uint64_t wire_len,
+                              const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                              uint32_t n_delivered, int is_server, int enable,
+                              const uint32_t* mask_keys, uint32_t flags, int pending_opcode,
+                              uint64_t pending_bytes, const uint8_t* carry, uint64_t carry_len,
+                              uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                              uint32_t max_answers, uint8_t* open, uint64_t open_cap,
+                              uvhttp_ws_answer_conn_t* conn_result,
+                              uvhttp_ws_reply_conn_t* reply_conn);
 
 /* ---- relay of data messages: the room server's broadcast built on the device after a decode - */
 /* The reference's other send path is uvhttp_server_ws_broadcast (src/uvhttp_server.c:1626-1657):

@@ -220,6 +220,29 @@ class EchoSummary(C.Structure):
         return {k: getattr(self, k) for k in ("out_bytes", "open_bytes", "n_echoes", "status")}
 
 
+ANSWER_SERVER_SEND, ANSWER_REPLY_AFTER_CLOSE = 0x1, 0x2  # UVHTTP_WS_ANSWER_*; statuses are ECHO_*
+
+
+class AnswerConn(C.Structure):
+    """uvhttp_ws_answer_conn_t (32 B)."""
+    _fields_ = [("first_answer", C.c_uint32), ("n_answers", C.c_uint32), ("out_len", C.c_uint64),
+                ("open_len", C.c_uint64), ("status", C.c_uint8), ("open_opcode", C.c_uint8),
+                ("closed", C.c_uint8), ("reserved", C.c_uint8), ("n_replies", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("first_answer", "n_answers", "out_len", "open_len", "status",
+                                              "open_opcode", "closed", "n_replies")}
+
+
+class AnswerSummary(C.Structure):
+    """uvhttp_ws_answer_summary_t (32 B)."""
+    _fields_ = [("out_bytes", C.c_uint64), ("open_bytes", C.c_uint64), ("n_answers", C.c_uint32),
+                ("n_replies", C.c_uint32), ("n_closed_conns", C.c_uint32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 RELAY_BAD_ROOM = 5  # UVHTTP_WS_RELAY_BAD_ROOM, beside the ECHO_* statuses
 
 
@@ -486,6 +509,14 @@ def load_library(path: str) -> C.CDLL:
         "uvhttp_ws_echo_messages": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, C.c_int,
                                               u64, vp, u64, vp, u64, vp, u32, vp, u64,
                                               C.POINTER(EchoConn)]),
+        "uvhttp_ws_gpu_answer_messages_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32,
+                                                            vp, u64, vp, vp, u64, vp, u32, vp, u32, vp, u64,
+                                                            vp, vp, vp, vp, vp]),
+        "uvhttp_ws_gpu_answer_messages_inplace": (C.c_int, [vp, vp, u64, vp, u32, vp, i32, vp, u32, vp, u64,
+                                                            vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp]),
+        "uvhttp_ws_answer_messages": (C.c_int, [vp, u64, vp, u32, u32, C.c_int, C.c_int, vp, u32, C.c_int,
+                                                u64, vp, u64, vp, u64, vp, u32, vp, u64,
+                                                C.POINTER(AnswerConn), C.POINTER(ReplyConn)]),
         "uvhttp_ws_gpu_relay_messages_streams": (C.c_int, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u32,
                                                            vp, u64, vp, vp, u64, vp, u32, vp, vp, u32, vp,
                                                            u32, vp, u64, vp, vp, vp, vp]),
@@ -795,6 +826,37 @@ def echo_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, m
     ok = res.status != ECHO_ERR_CAPACITY
     return (bytes(out)[: res.out_len if ok else 0], list(off),
             bytes(opn)[: res.open_len if ok else 0] if want_open else b"", res.as_dict())
+
+
+def answer_messages(wire, desc, first_frame, n_delivered, is_server=1, enable=1, mask_keys=None,
+                    flags=0, pending_opcode=0, pending_bytes=0, carry=None, out_cap=None,
+                    max_answers=None, open_cap=None, want_open=True, wire_len=None):
+    """uvhttp_ws_answer_messages: the host twin of GpuEngine.answer_messages_streams / _inplace for
+    one connection: its echoes and control replies as one run in frame order.  Arguments as
+    echo_messages; mask_keys has one key per answer slot.  -> (out bytes [out_len], out_off list
+    [max_answers + 1], open bytes [open_len], AnswerConn.as_dict(), ReplyConn.as_dict())."""
+    wb = _host_buf(wire)
+    db = _host_buf(desc)
+    n = len(wire) if wire_len is None else wire_len
+    carry = b"" if carry is None else bytes(carry)
+    max_answers = n_delivered if max_answers is None else max_answers
+    out_cap = 14 * n_delivered + n + len(carry) if out_cap is None else out_cap
+    open_cap = n + len(carry) if open_cap is None else open_cap
+    out = (C.c_uint8 * max(1, out_cap))()
+    opn = (C.c_uint8 * max(1, open_cap))() if want_open else None
+    off = (C.c_uint64 * (max_answers + 1))()
+    kb = None if mask_keys is None else (C.c_uint32 * max(1, len(mask_keys)))(*mask_keys)
+    cb = (C.c_uint8 * max(1, len(carry))).from_buffer_copy(carry or b"\0")
+    res, rep = AnswerConn(), ReplyConn()
+    rc = lib().uvhttp_ws_answer_messages(wb, n, db, first_frame, n_delivered, is_server, enable, kb,
+                                         flags, pending_opcode, pending_bytes, cb, len(carry), out,
+                                         out_cap, off, max_answers, opn, open_cap, C.byref(res),
+                                         C.byref(rep))
+    if rc != 0:
+        raise ValueError("uvhttp_ws_answer_messages: bad argument")
+    ok = res.status != ECHO_ERR_CAPACITY
+    return (bytes(out)[: res.out_len if ok else 0], list(off),
+            bytes(opn)[: res.open_len if ok else 0] if want_open else b"", res.as_dict(), rep.as_dict())
 
 
 def relay_messages(wire, desc, max_frames, streams, results, room, n_rooms, enable=None, flags=0,
@@ -1400,6 +1462,61 @@ class GpuEngine:
             open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
             C.c_void_p(summary.data_ptr()), self._stream(stream)), "echo_messages_inplace")
         return out, out_off, open_off, conn, summary
+
+    def answer_messages_streams(self, wire, desc, max_frames, streams_dev, results, n_streams,
+                                max_answers, out_cap, enable=None, mask_keys=None, flags=0, carry=None,
+                                carry_len=0, carry_off=None, out=None, out_off=None, runs=None,
+                                run_stride=8, open=None, open_cap=0, open_off=None, conn=None,
+                                summary=None, reply_conn=None, wire_len=None, stream=None):
+        """uvhttp_ws_gpu_answer_messages_streams: echo_messages_streams' echoes and
+        control_replies_streams' PONGs and CLOSE echoes as ONE run per connection, every answer
+        where its frame stood (the order the reference sends in).  Arguments as
+        echo_messages_streams; flags are ANSWER_*; reply_conn = a device tensor of n_streams 16-byte
+        uvhttp_ws_reply_conn_t for close_frames_streams (or None).  Returns (out, out_off, open_off,
+        conn, summary): conn holds n_streams uvhttp_ws_answer_conn_t, summary the
+        uvhttp_ws_answer_summary_t."""
+        out, out_off, open_off, conn, summary = self._echo_out(n_streams, max_answers, out_cap, out,
+                                                               out_off, open_off, conn, summary)
+        self._check(self._L.uvhttp_ws_gpu_answer_messages_streams(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), max_frames, C.c_void_p(streams_dev.data_ptr()),
+            C.c_void_p(results.data_ptr()), n_streams, self._ptr(enable), self._ptr(mask_keys), flags,
+            self._ptr(carry), carry_len, self._ptr(carry_off), C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_answers, self._ptr(runs), run_stride, self._ptr(open),
+            open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
+            C.c_void_p(summary.data_ptr()), self._ptr(reply_conn), self._stream(stream)),
+            "answer_messages_streams")
+        return out, out_off, open_off, conn, summary
+
+    def answer_messages_inplace(self, wire, desc, n_frames, batch_summary, max_answers, out_cap,
+                                is_server=1, mask_keys=None, flags=0, out=None, out_off=None, runs=None,
+                                run_stride=8, open=None, open_cap=0, open_off=None, conn=None,
+                                summary=None, reply_conn=None, wire_len=None, stream=None):
+        """uvhttp_ws_gpu_answer_messages_inplace after decode_inplace, or after decode_compact with
+        the arena as `wire`: one connection.  Returns as answer_messages_streams."""
+        out, out_off, open_off, conn, summary = self._echo_out(1, max_answers, out_cap, out, out_off,
+                                                               open_off, conn, summary)
+        self._check(self._L.uvhttp_ws_gpu_answer_messages_inplace(
+            self.h, C.c_void_p(wire.data_ptr()), wire.numel() if wire_len is None else wire_len,
+            C.c_void_p(desc.data_ptr()), n_frames, C.c_void_p(batch_summary.data_ptr()), is_server,
+            self._ptr(mask_keys), flags, C.c_void_p(out.data_ptr()), out_cap,
+            C.c_void_p(out_off.data_ptr()), max_answers, self._ptr(runs), run_stride, self._ptr(open),
+            open_cap, C.c_void_p(open_off.data_ptr()), C.c_void_p(conn.data_ptr()),
+            C.c_void_p(summary.data_ptr()), self._ptr(reply_conn), self._stream(stream)),
+            "answer_messages_inplace")
+        return out, out_off, open_off, conn, summary
+
+    @staticmethod
+    def read_answer_conns(conn, n):
+        """host copy of the first n per-connection answer results -> [dict] (AnswerConn.as_dict)"""
+        sz = C.sizeof(AnswerConn)
+        raw = conn[: n * sz].cpu().numpy().tobytes()
+        return [AnswerConn.from_buffer_copy(raw, k * sz).as_dict() for k in range(n)]
+
+    @staticmethod
+    def read_answer_summary(summary) -> dict:
+        raw = summary[: C.sizeof(AnswerSummary)].cpu().numpy().tobytes()
+        return AnswerSummary.from_buffer_copy(raw).as_dict()
 
     def relay_messages_streams(self, wire, desc, max_frames, streams_dev, results, n_streams, room,
                                n_rooms, max_frames_out, out_cap, enable=None, flags=0, carry=None,

@@ -72,6 +72,31 @@
 // The kernels both calls use and the relay changes (init, conns, size, offsets, finish, emit) are
 // templates over the argument type, EcArgs or RlArgs: the echo's instances are the kernels they
 // were, launched as they were, and only the relay's carry the room order and its arguments.
+//
+// The answers (uvhttp_ws_gpu_answer_messages_streams / _inplace) are the echo's launch sequence
+// over a third argument type, AnArgs: a PONG or a CLOSE echo is one more record of the same scan,
+// in the slot its frame's descriptor gives it, so a connection's run is its echoes and its control
+// replies in frame order.  What AnArgs' instances add:
+//
+//   k_echo_classify  also marks a delivered PING / CLOSE of an active connection (kCtl, the
+//                    reply's payload length in the word) and range-checks the reply's payload
+//   k_echo_size      the lane of such a frame decides whether it is answered (not after the first
+//                    CLOSE unless the flag says so, connection not bad) and sizes the reply: 2
+//                    header bytes, 4 more when masked, the payload.  A third aggregate, replies
+//                    << 35 | their payload bytes, for the per-connection reply counts
+//   k_echo_top       ... its prefixes
+//   k_echo_offsets   the reply's record on its own lane: b0 = 0x8A or 0x88, one = 1, g = fend = f,
+//                    src0 = the control frame's payload_off; rbeg / rend per connection
+//   k_echo_finish    the answer result (closed, n_replies), the optional reply table that
+//                    close_frames_streams reads, the answer summary
+//   k_echo_emit      the same byte mover.  dsum counts data payloads only, so a control record's
+//                    bytes are never looked up there: every path that locates a source byte of a
+//                    record with one = 1 — the vector path, and in this instance the long way's
+//                    whole-vector and byte-wise paths (emit_vector<true>, payload_byte<true>) —
+//                    takes it from src0
+//
+// k_echo_classify became a template for this (its EcArgs instance is the kernel it was, and the
+// relay still launches that one); no other instance of the echo or the relay changed.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -98,6 +123,12 @@ constexpr uint64_t kStart = 1ull << 4;   // ... with opcode 1 or 2
 constexpr uint64_t kFin = 1ull << 5;     // ... with FIN
 constexpr uint64_t kCarryHead = 1ull << 6;  // kFirst of a connection that carries a message in
 constexpr uint64_t kEcho = 1ull << 7;    // the FIN frame of an echoed message (k_echo_size)
+// ... and the answers' (AnArgs) only:
+constexpr uint64_t kCtl = 1ull << 8;     // a delivered PING / CLOSE of an active connection, range checked
+constexpr uint64_t kCtlClose = 1ull << 9;  // ... a CLOSE (the reply is a CLOSE, else a PONG)
+constexpr uint64_t kReply = 1ull << 10;  // answered (k_echo_size)
+constexpr int kCtlLenShift = 16;         // bits 16-22: the reply's payload length
+constexpr uint64_t kCtlLenMask = 0x7F;
 // bits 32-63: the connection
 
 // the word per connection (cstate): bits 0-7 the static status, then
@@ -179,6 +210,7 @@ struct EcArgs {
     uint32_t* tmap;         // [tiles of d_out] the record that holds the tile's first byte
     uint32_t* omap;         // [tiles of d_open] likewise
     static constexpr bool kRelay = false;
+    static constexpr bool kAnswer = false;
 };
 
 // The relay's arguments (uvhttp_ws_gpu_relay_messages_streams): the echo's and its own.  The
@@ -209,6 +241,21 @@ struct RlArgs : EcArgs {
     uint64_t* rbytes;       // likewise its first frame's offset
     uint32_t* written;      // [1] records k_echo_offsets wrote: the emit runs only when all were
 };
+
+// The answers' arguments (uvhttp_ws_gpu_answer_messages_streams / _inplace): the echo's, with
+// PONGs and CLOSE echoes as records of the same scan.  conn / sum point at the answer structs,
+// which begin as the echo's.
+struct AnArgs : EcArgs {
+    static constexpr bool kAnswer = true;
+    uvhttp_ws_reply_conn_t* reply_conn;  // or null
+    // ... its scratch
+    uint64_t* agg_rep;      // [blocks] replies << 35 | their payload bytes, then inclusive
+    const uint64_t* tot_rep;  // &agg_rep[blocks - 1], null when there is no descriptor
+    uint64_t* rbeg;         // [n_streams] that sum before the connection's first frame ...
+    uint64_t* rend;         // ... and up to its last
+};
+// replies << 35 | payload bytes: at most 2^28 replies of at most 125 bytes
+constexpr int kRepShift = 35;
 
 struct LastOp {  // the later mark
     __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return b ? b : a; }
@@ -304,6 +351,9 @@ __device__ __forceinline__ EcTotals totals(const EcArgs& a) {
     return t;
 }
 
+// the reply of a control frame the answers' classify marked
+__device__ __forceinline__ uint64_t ctl_len(uint64_t e) { return (e >> kCtlLenShift) & kCtlLenMask; }
+
 __device__ __forceinline__ uint32_t header_bytes(uint64_t len, bool masked) {
     return (len <= 125 ? 2u : len <= 65535 ? 4u : 10u) + (masked ? 4u : 0u);
 }
@@ -317,6 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_init(A a) {
         a.open_off[0] = 0;
         if constexpr (A::kRelay) *a.written = 0;
     }
+    static_assert(sizeof(uvhttp_ws_answer_summary_t) == sizeof(uvhttp_ws_echo_summary_t), "zeroed through the echo's type");
     if (i < a.max_frames) a.marks[i] = 0;
 }
 
@@ -331,6 +382,10 @@ __global__ __launch_bounds__(kBlock) void k_echo_conns(A a) {
     a.bbeg[s] = 0;
     a.bend[s] = 0;
     a.ofend[s] = 0;
+    if constexpr (A::kAnswer) {
+        a.rbeg[s] = 0;
+        a.rend[s] = 0;
+    }
     uint32_t st = 0;
     const uint64_t pend = conn_pending(a, (uint32_t)s);
     if (!a.enable || a.enable[s] != 0) {
@@ -409,7 +464,8 @@ __device__ __forceinline__ uint64_t posted_of(uint64_t e, uint64_t f) {
     return 0;
 }
 
-__global__ __launch_bounds__(kBlock) void k_echo_classify(EcArgs a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void k_echo_classify(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = f < a.max_frames;
@@ -437,6 +493,15 @@ __global__ __launch_bounds__(kBlock) void k_echo_classify(EcArgs a) {
                         plen = len;
                         e |= kData | (op != UVHTTP_WS_OPCODE_CONTINUATION ? kStart : 0) |
                              ((d.flags & UVHTTP_WS_FLAG_FIN) ? kFin : 0);
+                    }
+                }
+                if constexpr (A::kAnswer) {
+                    if ((cs & kCActive) && (op == UVHTTP_WS_OPCODE_PING || op == UVHTTP_WS_OPCODE_CLOSE)) {
+                        uint64_t len = d.payload_len;  // the reply's: k_rp_classify's rule
+                        if (op == UVHTTP_WS_OPCODE_CLOSE && len < 2) len = 0;
+                        if (len > 125) len = 125;
+                        if (len != 0 && !range_ok(a.wire_len, d.payload_off, len)) a.bad[conn] = 1;
+                        else e |= kCtl | (op == UVHTTP_WS_OPCODE_CLOSE ? kCtlClose : 0) | (len << kCtlLenShift);
                     }
                 }
             }
@@ -508,13 +573,30 @@ __global__ __launch_bounds__(kBlock) void k_echo_size(A a) {
                 a.ofend[conn] = (uint32_t)f;
             }
         }
+        if constexpr (A::kAnswer) {
+            // a PING or CLOSE is answered on its own lane: not after the first CLOSE unless the
+            // flag says to go on, and never for a bad connection
+            if ((e & kCtl) && a.bad[conn] == 0 &&
+                ((a.flags & UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE) || (uint32_t)f <= a.first_close[conn])) {
+                e |= kReply;
+                a.elem[f] = e;
+                bytes = 2u + (conn_masked(a, conn) ? 4u : 0u) + ctl_len(e);
+            }
+        }
     }
     uint64_t tot_c, tot_b;
-    (void)block_scan((e & kEcho) ? 1 : 0, AddOp(), s_wave, &tot_c);
+    bool counts = (e & kEcho) != 0;
+    if constexpr (A::kAnswer) counts = (e & (kEcho | kReply)) != 0;
+    (void)block_scan(counts ? 1 : 0, AddOp(), s_wave, &tot_c);
     (void)block_scan(bytes, AddOp(), s_wave, &tot_b);
     if (threadIdx.x == 0) {
         a.agg_cnt[blockIdx.x] = tot_c;
         a.agg_bytes[blockIdx.x] = tot_b;
+    }
+    if constexpr (A::kAnswer) {
+        uint64_t tot_r;
+        (void)block_scan((e & kReply) ? (1ull << kRepShift) | ctl_len(e) : 0, AddOp(), s_wave, &tot_r);
+        if (threadIdx.x == 0) a.agg_rep[blockIdx.x] = tot_r;
     }
 }
 
@@ -528,7 +610,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t e = f < a.max_frames ? a.elem[f] : 0;
-    const bool echo = (e & kEcho) != 0;
+    bool echo = (e & kEcho) != 0;  // an answer: an echo, or (the answers') a reply
     const uint32_t conn = (uint32_t)(e >> 32);
     uint64_t v = 0, len = 0, mine = 0;
     bool masked = false;
@@ -537,6 +619,16 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
         len = message_len(a, v, f, a.desc[f].payload_len, conn);
         masked = conn_masked(a, conn);
         mine = header_bytes(len, masked) + len;
+    }
+    bool reply = false;
+    if constexpr (A::kAnswer) {
+        reply = (e & kReply) != 0;
+        if (reply) {
+            echo = true;
+            len = ctl_len(e);
+            masked = conn_masked(a, conn);
+            mine = 2u + (masked ? 4u : 0u) + len;
+        }
     }
     uint64_t tot;
     const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + block_scan(echo ? 1 : 0, AddOp(), s_wave, &tot);
@@ -551,6 +643,14 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
         if (e & kLast) {
             a.cend[conn] = (uint32_t)cnt;
             a.bend[conn] = bytes;
+        }
+    }
+    if constexpr (A::kAnswer) {
+        const uint64_t mine_r = reply ? (1ull << kRepShift) | len : 0;
+        const uint64_t rep = (blockIdx.x ? a.agg_rep[blockIdx.x - 1] : 0) + block_scan(mine_r, AddOp(), s_wave, &tot);
+        if (e & kIn) {
+            if (e & kFirst) a.rbeg[conn] = rep - mine_r;
+            if (e & kLast) a.rend[conn] = rep;
         }
     }
     if (!echo || !totals(a).fits) return;
@@ -569,6 +669,28 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
             at > t.bytes || mine > t.bytes - at)
             return;
         atomicAdd(a.written, 1u);
+    }
+    if constexpr (A::kAnswer) {
+        if (reply) {  // one fragment, the control frame's own payload: never looked up in dsum
+            a.out_off[j] = at;
+            EcRec r;
+            r.dbase = a.dsum[f];
+            r.len = len;
+            r.carry_src = 0;
+            r.carry_len = 0;
+            r.src0 = a.desc[f].payload_off;
+            r.g = (uint32_t)f;
+            r.fend = (uint32_t)f;
+            r.key = masked ? a.keys[j] : 0u;
+            r.hdr = (uint8_t)(masked ? 6 : 2);
+            r.b0 = (uint8_t)(0x80u | ((e & kCtlClose) ? UVHTTP_WS_OPCODE_CLOSE : UVHTTP_WS_OPCODE_PONG));
+            r.masked = masked ? 1 : 0;
+            r.one = 1;
+            r.pad = 0;
+            a.rec[j] = r;
+            map_tiles(a.tmap, (uint32_t)j, at, mine);
+            return;
+        }
     }
     const uint64_t g = (v >> 2) - 1;
     const bool carried = (v & 3) == kMsgCarried;
@@ -623,6 +745,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(A a) {
     if constexpr (!A::kRelay) inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
     const uint64_t inc_o = (blockIdx.x ? a.agg_co[blockIdx.x - 1] : 0) + block_scan(ol, AddOp(), s_wave, &tot);
     const EcTotals t = totals(a);
+    [[maybe_unused]] bool closed = false;
     if (live) {
         uvhttp_ws_echo_conn_t r = {};
         if (!t.fits) {
@@ -659,14 +782,65 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(A a) {
             a.orec[s] = o;
             if (a.open) map_tiles(a.omap, (uint32_t)s, inc_o - ol, ol);
         }
-        a.conn[s] = r;
+        if constexpr (A::kAnswer) {
+            // the answer's result begins as the echo's; then closed and the replies among the answers
+            static_assert(offsetof(uvhttp_ws_answer_conn_t, first_answer) == offsetof(uvhttp_ws_echo_conn_t, first_echo) &&
+                              offsetof(uvhttp_ws_answer_conn_t, n_answers) == offsetof(uvhttp_ws_echo_conn_t, n_echoes) &&
+                              offsetof(uvhttp_ws_answer_conn_t, out_len) == offsetof(uvhttp_ws_echo_conn_t, out_len) &&
+                              offsetof(uvhttp_ws_answer_conn_t, open_len) == offsetof(uvhttp_ws_echo_conn_t, open_len) &&
+                              offsetof(uvhttp_ws_answer_conn_t, status) == offsetof(uvhttp_ws_echo_conn_t, status) &&
+                              offsetof(uvhttp_ws_answer_conn_t, open_opcode) == offsetof(uvhttp_ws_echo_conn_t, open_opcode),
+                          "the answer result begins as the echo's");
+            closed = a.first_close[s] != kNone;
+            const uint64_t rp = a.rend[s] - a.rbeg[s];
+            const uint32_t n_rep = (uint32_t)(rp >> kRepShift);
+            const uint64_t rep_bytes = (rp & ((1ull << kRepShift) - 1)) + (uint64_t)n_rep * (conn_masked(a, (uint32_t)s) ? 6u : 2u);
+            uvhttp_ws_answer_conn_t w = {};
+            w.first_answer = r.first_echo;
+            w.n_answers = r.n_echoes;
+            w.out_len = r.out_len;
+            w.open_len = r.open_len;
+            w.status = r.status;
+            w.open_opcode = r.open_opcode;
+            if (t.fits) {
+                w.closed = closed ? 1 : 0;
+                w.n_replies = n_rep;
+            }
+            reinterpret_cast<uvhttp_ws_answer_conn_t*>(a.conn)[s] = w;
+            if (a.reply_conn) {
+                uvhttp_ws_reply_conn_t q = {};
+                q.closed = closed ? 1 : 0;
+                if (!t.fits) {
+                    q.status = UVHTTP_WS_REPLY_ERR_CAPACITY;
+                } else {
+                    q.n_replies = n_rep;
+                    q.out_len = rep_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)rep_bytes;
+                    q.status = r.status == UVHTTP_WS_ECHO_BAD_RANGE ? UVHTTP_WS_REPLY_BAD_RANGE
+                               : r.status == UVHTTP_WS_ECHO_NO_KEYS ? UVHTTP_WS_REPLY_NO_KEYS : UVHTTP_WS_REPLY_OK;
+                }
+                a.reply_conn[s] = q;
+            }
+        } else {
+            a.conn[s] = r;
+        }
         if (a.runs) {
             uint32_t* run = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.runs) + s * a.run_stride);
             run[0] = r.first_echo;
             run[1] = r.n_echoes;
         }
     }
-    if (s == 0) {
+    if constexpr (A::kAnswer) {
+        uvhttp_ws_answer_summary_t* sum = reinterpret_cast<uvhttp_ws_answer_summary_t*>(a.sum);
+        const uint64_t mc = __ballot(closed);
+        if ((threadIdx.x & 63) == 0 && mc) atomicAdd(&sum->n_closed_conns, (uint32_t)__popcll(mc));
+        if (s == 0) {
+            sum->out_bytes = t.bytes;
+            sum->open_bytes = t.open;
+            sum->n_answers = (uint32_t)t.cnt;
+            sum->n_replies = a.tot_rep ? (uint32_t)(*a.tot_rep >> kRepShift) : 0u;
+            sum->status = t.fits ? UVHTTP_WS_ECHO_OK : UVHTTP_WS_ECHO_ERR_CAPACITY;
+        }
+    } else if (s == 0) {
         a.sum->out_bytes = t.bytes;
         a.sum->open_bytes = t.open;
         a.sum->n_echoes = (uint32_t)t.cnt;
@@ -860,9 +1034,15 @@ __device__ __forceinline__ uint64_t last_le(const uint64_t* t, uint64_t lo, uint
     return lo;
 }
 
-// the unmasked payload byte at message offset m of record r (0 where a broken table leaves none)
+// the unmasked payload byte at message offset m of record r (0 where a broken table leaves none).
+// kOne (the answers'): a record with one fragment takes it from src0 — a control frame's payload
+// is not counted in dsum, so it must never be searched for there
+template <bool kOne>
 __device__ __forceinline__ uint32_t payload_byte(const EcArgs& a, const EcRec& r, uint64_t m) {
     if (m < r.carry_len) return a.carry[r.carry_src + m];
+    if constexpr (kOne) {
+        if (r.one) return a.wire[r.src0 + (m - r.carry_len)];
+    }
     if (r.g > r.fend) return 0;
     const uint64_t q = r.dbase + (m - r.carry_len);
     const uint64_t i = last_le(a.dsum, r.g, r.fend, q);
@@ -883,6 +1063,7 @@ struct EcDst {
 // one vector the long way: its source frame by a search over dsum when it is payload of one
 // fragment, else byte by byte — header bytes, a join of two sources or of two records, or the
 // output's last bytes
+template <bool kOne>
 __device__ __forceinline__ void emit_vector(const EcArgs& a, const EcDst& o, uint64_t x, uint64_t ri) {
     EcRec r = o.recs[ri];
     uint64_t r_off = o.offs[ri];
@@ -892,6 +1073,8 @@ __device__ __forceinline__ void emit_vector(const EcArgs& a, const EcDst& o, uin
         const uint8_t* src = nullptr;
         if (m + 16 <= r.carry_len) {
             src = a.carry + r.carry_src + m;
+        } else if (kOne && m >= r.carry_len && r.one) {
+            src = a.wire + r.src0 + (m - r.carry_len);
         } else if (m >= r.carry_len && r.g <= r.fend) {
             const uint64_t q = r.dbase + (m - r.carry_len);
             const uint64_t i = last_le(a.dsum, r.g, r.fend, q);
@@ -926,7 +1109,7 @@ __device__ __forceinline__ void emit_vector(const EcArgs& a, const EcDst& o, uin
             v = header_byte(r, (uint32_t)q);
         } else {
             const uint64_t m = q - r.hdr;
-            v = m < r.len ? payload_byte(a, r, m) : 0u;
+            v = m < r.len ? payload_byte<kOne>(a, r, m) : 0u;
             if (r.masked) v ^= (r.key >> (8 * (uint32_t)(m & 3u))) & 0xFFu;
         }
         w[b >> 2] |= (v & 0xFFu) << (8 * (b & 3));
@@ -1043,7 +1226,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_emit(A a, uint64_t tile_base, u
         if (!(slow >> k & 1u)) continue;
         static_assert(kBatch == 4, "the selects below");
         const uint64_t ri = k == 0 ? rl[0] : k == 1 ? rl[1] : k == 2 ? rl[2] : rl[3];
-        emit_vector(a, o, lo_b + ((uint64_t)k * kBlock + threadIdx.x) * 16, ri);
+        emit_vector<A::kAnswer>(a, o, lo_b + ((uint64_t)k * kBlock + threadIdx.x) * 16, ri);
     }
     }
 }
@@ -1054,6 +1237,7 @@ template <class A>
 int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     constexpr bool relay = A::kRelay;
     static_assert(sizeof(uvhttp_ws_echo_conn_t) == 32 && sizeof(uvhttp_ws_echo_summary_t) == 32, "ABI");
+    static_assert(sizeof(uvhttp_ws_answer_conn_t) == 32 && sizeof(uvhttp_ws_answer_summary_t) == 32, "ABI");
     const uint64_t F = a.max_frames, S = a.n_streams, E = a.max_echoes;
     const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
     const uint32_t grid_s = (uint32_t)((S + kBlock - 1) / kBlock);
@@ -1081,6 +1265,9 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     const size_t o_aggh = take(R * ns * 8), o_aggpc = take(R * ns * 8), o_aggpb = take(R * ns * 8);
     const size_t o_skey0 = take(R * S * 4), o_skey1 = take(R * S * 4), o_sidx0 = take(R * S * 4), o_sidx1 = take(R * S * 4);
     const size_t o_hist = take(R * ns * kBlock * 4), o_rcnt = take(R * S * 4), o_written = take(R * 4);
+    // the answers' (nothing for the others)
+    const uint64_t N = A::kAnswer ? 1 : 0;
+    const size_t o_arep = take(N * nb * 8), o_rbeg = take(N * S * 8), o_rend = take(N * S * 8);
     // radix passes: the bits of the largest key, n_rooms
     uint32_t passes = 0;
     if constexpr (relay)
@@ -1135,6 +1322,12 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
         a.rcnt = reinterpret_cast<uint32_t*>(mem + o_rcnt);
         a.written = reinterpret_cast<uint32_t*>(mem + o_written);
     }
+    if constexpr (A::kAnswer) {
+        a.agg_rep = reinterpret_cast<uint64_t*>(mem + o_arep);
+        a.rbeg = reinterpret_cast<uint64_t*>(mem + o_rbeg);
+        a.rend = reinterpret_cast<uint64_t*>(mem + o_rend);
+        a.tot_rep = blocks && grid_s ? a.agg_rep + (blocks - 1) : nullptr;
+    }
     const bool frames = blocks && grid_s;  // else no echo: the totals are 0
     a.tot_cnt = frames ? a.agg_cnt + (blocks - 1) : nullptr;
     a.tot_bytes = frames ? a.agg_bytes + (blocks - 1) : nullptr;
@@ -1146,13 +1339,16 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     if (frames) {
         hipLaunchKernelGGL(k_echo_reduce, dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, blocks);
-        hipLaunchKernelGGL(k_echo_classify, dim3(blocks), dim3(kBlock), 0, s, base);
+        // (the relay classifies as the echo does: the echo's instance)
+        if constexpr (A::kAnswer) hipLaunchKernelGGL((k_echo_classify<A>), dim3(blocks), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_echo_classify<EcArgs>), dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_d, blocks);
         hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_post, blocks);
         hipLaunchKernelGGL(k_echo_prefix, dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_size<A>), dim3(blocks), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cnt, blocks);
         hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_bytes, blocks);
+        if constexpr (A::kAnswer) hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_rep, blocks);
     }
     if (grid_s) {
         hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, base, 1);
@@ -1363,4 +1559,100 @@ extern "C" int uvhttp_ws_gpu_relay_messages_streams(
                             "relay_messages_streams: max_frames or max_frames_out > 2^28 or n_streams > 2^31");
     if (rc != UVHTTP_WS_GPU_OK) return rc;
     return ec_run(e, a, stream, "relay_messages_streams launch");
+}
+
+// ---- the answers: echoes and control replies in one run ------------------------------------------
+
+namespace {
+
+int an_check(uvhttp_ws_gpu_engine_t* e, const AnArgs& a, const char* flag_msg, const char* align_msg) {
+    if (a.flags & ~(UVHTTP_WS_ANSWER_SERVER_SEND | UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE))
+        return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, flag_msg);
+    if ((uintptr_t)a.reply_conn & 3u) return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, align_msg);
+    return UVHTTP_WS_GPU_OK;
+}
+
+}  // namespace
+
+extern "C" int uvhttp_ws_gpu_answer_messages_streams(
+    uvhttp_ws_gpu_engine_t* e, const uint8_t* d_wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+    uint32_t max_frames, const uvhttp_ws_stream_t* d_streams, const uvhttp_ws_stream_result_t* d_results,
+    uint32_t n_streams, const uint8_t* d_enable, const uint32_t* d_mask_keys, uint32_t flags, const uint8_t* d_carry,
+    uint64_t carry_len, const uint64_t* d_carry_off, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+    uint32_t max_answers, uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+    uint64_t* d_open_off, uvhttp_ws_answer_conn_t* d_conn, uvhttp_ws_answer_summary_t* d_summary,
+    uvhttp_ws_reply_conn_t* d_reply_conn, void* stream) {
+    static_assert(UVHTTP_WS_ANSWER_SERVER_SEND == UVHTTP_WS_ECHO_SERVER_SEND, "k_echo_size / k_echo_offsets test the echo's bit");
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    if (!d_streams) return uvws_set_err(e, UVHTTP_WS_GPU_EINVAL, "answer_messages_streams: NULL argument");
+    AnArgs a = {};
+    a.wire = d_wire;
+    a.wire_len = wire_len;
+    a.desc = d_desc;
+    a.max_frames = max_frames;
+    a.n_streams = n_streams;
+    a.streams = d_streams;
+    a.results = d_results;
+    a.enable = d_enable;
+    a.keys = d_mask_keys;
+    a.flags = flags;
+    a.carry = d_carry;
+    a.carry_len = carry_len;
+    a.carry_off = d_carry_off;
+    a.out = d_out;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    a.max_echoes = max_answers;
+    a.runs = d_runs;
+    a.run_stride = run_stride;
+    a.open = d_open;
+    a.open_cap = open_cap;
+    a.open_off = d_open_off;
+    a.conn = reinterpret_cast<uvhttp_ws_echo_conn_t*>(d_conn);
+    a.sum = reinterpret_cast<uvhttp_ws_echo_summary_t*>(d_summary);
+    a.reply_conn = d_reply_conn;
+    int rc = ec_check(e, a, "answer_messages_streams: NULL argument", "answer_messages_streams: misaligned argument",
+                      "answer_messages_streams: max_frames or max_answers > 2^28, n_streams > 2^31 or a bad run_stride");
+    if (rc == UVHTTP_WS_GPU_OK)
+        rc = an_check(e, a, "answer_messages_streams: unknown flags", "answer_messages_streams: misaligned argument");
+    if (rc != UVHTTP_WS_GPU_OK) return rc;
+    return ec_run(e, a, stream, "answer_messages_streams launch");
+}
+
+extern "C" int uvhttp_ws_gpu_answer_messages_inplace(
+    uvhttp_ws_gpu_engine_t* e, const uint8_t* d_wire, uint64_t wire_len, const uvhttp_ws_frame_desc_t* d_desc,
+    uint32_t n_frames, const uvhttp_ws_batch_summary_t* d_batch_summary, int32_t is_server,
+    const uint32_t* d_mask_keys, uint32_t flags, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off,
+    uint32_t max_answers, uint32_t* d_runs, uint32_t run_stride, uint8_t* d_open, uint64_t open_cap,
+    uint64_t* d_open_off, uvhttp_ws_answer_conn_t* d_conn, uvhttp_ws_answer_summary_t* d_summary,
+    uvhttp_ws_reply_conn_t* d_reply_conn, void* stream) {
+    if (!e) return UVHTTP_WS_GPU_EINVAL;
+    AnArgs a = {};
+    a.wire = d_wire;
+    a.wire_len = wire_len;
+    a.desc = d_desc;
+    a.max_frames = n_frames;
+    a.n_streams = 1;
+    a.bsum = d_batch_summary;
+    a.is_server = is_server;
+    a.keys = d_mask_keys;
+    a.flags = flags;
+    a.out = d_out;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    a.max_echoes = max_answers;
+    a.runs = d_runs;
+    a.run_stride = run_stride;
+    a.open = d_open;
+    a.open_cap = open_cap;
+    a.open_off = d_open_off;
+    a.conn = reinterpret_cast<uvhttp_ws_echo_conn_t*>(d_conn);
+    a.sum = reinterpret_cast<uvhttp_ws_echo_summary_t*>(d_summary);
+    a.reply_conn = d_reply_conn;
+    int rc = ec_check(e, a, "answer_messages_inplace: NULL argument", "answer_messages_inplace: misaligned argument",
+                      "answer_messages_inplace: n_frames or max_answers > 2^28 or a bad run_stride");
+    if (rc == UVHTTP_WS_GPU_OK)
+        rc = an_check(e, a, "answer_messages_inplace: unknown flags", "answer_messages_inplace: misaligned argument");
+    if (rc != UVHTTP_WS_GPU_OK) return rc;
+    return ec_run(e, a, stream, "answer_messages_inplace launch");
 }

@@ -943,6 +943,171 @@ int uvhttp_ws_echo_messages(const uint8_t* wire, uint64_t wire_len,
     return 0;
 }
 
+/* ---- answers: one connection's echoes and control replies in frame order -------------------- */
+/* The host twin of uvhttp_ws_gpu_answer_messages_streams / _inplace and the statement of their
+ * rule (include/uvhttp_ws_amd.h): what uvhttp_ws_process_data hands uvhttp_ws_send_frame as it
+ * goes — the PONG where the PING stood, the echo where the message's FIN frame stood, the CLOSE
+ * echo where the CLOSE stood — as one run of frames. */
+static uint64_t answer_ctl_len(const uvhttp_ws_frame_desc_t* d) {
+    uint64_t len = d->payload_len;
+    if (d->opcode == UVHTTP_WS_OPCODE_CLOSE && len < 2) len = 0;
+    return len > 125 ? 125 : len; /* a delivered control frame has at most 125 bytes */
+}
+
+int uvhttp_ws_answer_messages(const uint8_t* wire, uint64_t wire_len,
+                              const uvhttp_ws_frame_desc_t* desc, uint32_t first_frame,
+                              uint32_t n_delivered, int is_server, int enable,
+                              const uint32_t* mask_keys, uint32_t flags, int pending_opcode,
+                              uint64_t pending_bytes, const uint8_t* carry, uint64_t carry_len,
+                              uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                              uint32_t max_answers, uint8_t* open, uint64_t open_cap,
+                              uvhttp_ws_answer_conn_t* r, uvhttp_ws_reply_conn_t* q) {
+    if (r == NULL || out_off == NULL || (desc == NULL && n_delivered != 0) ||
+        (wire == NULL && wire_len != 0) || (out == NULL && out_cap != 0) ||
+        (carry == NULL && carry_len != 0) ||
+        (flags & ~(UVHTTP_WS_ANSWER_SERVER_SEND | UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE)) != 0)
+        return -1;
+    memset(r, 0, sizeof(*r));
+    if (q != NULL) memset(q, 0, sizeof(*q));
+    for (uint64_t j = 0; j <= max_answers; ++j) out_off[j] = 0;
+    /* closed: a CLOSE was delivered, whatever else holds */
+    for (uint32_t i = 0; i < n_delivered; ++i) {
+        const uvhttp_ws_frame_desc_t* d = &desc[(uint64_t)first_frame + i];
+        if (d->status == UVHTTP_WS_FRAME_OK && d->opcode == UVHTTP_WS_OPCODE_CLOSE) r->closed = 1;
+    }
+    if (q != NULL) q->closed = r->closed;
+    if (!enable) return 0; /* skipped as a whole */
+    const int masked = !is_server;
+    if (masked && mask_keys == NULL) {
+        r->status = UVHTTP_WS_ECHO_NO_KEYS;
+        if (q != NULL) q->status = UVHTTP_WS_REPLY_NO_KEYS;
+        return 0;
+    }
+    if (pending_bytes != 0 && carry_len != pending_bytes) {
+        r->status = UVHTTP_WS_ECHO_NO_CARRY;
+        return 0;
+    }
+    /* BAD_RANGE: every delivered data frame and every delivered PING / CLOSE, answered or not */
+    for (uint32_t i = 0; i < n_delivered; ++i) {
+        const uvhttp_ws_frame_desc_t* d = &desc[(uint64_t)first_frame + i];
+        if (d->status != UVHTTP_WS_FRAME_OK) continue;
+        uint64_t len;
+        if (echo_is_data(d)) len = d->payload_len;
+        else if (d->opcode == UVHTTP_WS_OPCODE_PING || d->opcode == UVHTTP_WS_OPCODE_CLOSE) len = answer_ctl_len(d);
+        else continue;
+        if (len != 0 && !utf8_range_ok(wire_len, d->payload_off, len)) {
+            r->status = UVHTTP_WS_ECHO_BAD_RANGE;
+            if (q != NULL) q->status = UVHTTP_WS_REPLY_BAD_RANGE;
+            return 0;
+        }
+    }
+    /* two passes over the same walk: size, then emit */
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t n = 0, bytes = 0, n_rep = 0, rep_bytes = 0;
+        int closed = 0;
+        int cur = pending_bytes != 0, cur_op = pending_opcode & 0x0F, carried = cur;
+        uint64_t cur_len = pending_bytes, lo = first_frame;
+        for (uint32_t i = 0; i < n_delivered; ++i) {
+            const uint64_t f = (uint64_t)first_frame + i;
+            const uvhttp_ws_frame_desc_t* d = &desc[f];
+            if (d->status != UVHTTP_WS_FRAME_OK) continue; /* not delivered */
+            if (d->opcode == UVHTTP_WS_OPCODE_PING || d->opcode == UVHTTP_WS_OPCODE_CLOSE) {
+                const int after = closed;
+                if (d->opcode == UVHTTP_WS_OPCODE_CLOSE) closed = 1;
+                if (after && !(flags & UVHTTP_WS_ANSWER_REPLY_AFTER_CLOSE)) continue;
+                const uint64_t len = answer_ctl_len(d), hdr = masked ? 6u : 2u;
+                if (pass == 1) {
+                    uint8_t* o = out + bytes;
+                    const uint32_t key = masked ? mask_keys[n] : 0u;
+                    o[0] = (uint8_t)(0x80u | (d->opcode == UVHTTP_WS_OPCODE_PING ? UVHTTP_WS_OPCODE_PONG
+                                                                                 : UVHTTP_WS_OPCODE_CLOSE));
+                    o[1] = (uint8_t)((masked ? 0x80u : 0u) | len);
+                    if (masked)
+                        for (int k = 0; k < 4; ++k) o[2 + k] = (uint8_t)(key >> (8 * k));
+                    for (uint64_t b = 0; b < len; ++b)
+                        o[hdr + b] = (uint8_t)(wire[d->payload_off + b] ^ (uint8_t)(key >> (8 * (b & 3))));
+                    out_off[n] = bytes;
+                }
+                n++;
+                n_rep++;
+                bytes += hdr + len;
+                rep_bytes += hdr + len;
+                continue;
+            }
+            if (!echo_is_data(d)) continue;
+            if (d->opcode != UVHTTP_WS_OPCODE_CONTINUATION) {
+                cur = 1;
+                cur_op = d->opcode;
+                carried = 0;
+                cur_len = 0;
+                lo = f;
+            } else if (!cur) {
+                continue; /* a CONTINUATION of nothing */
+            }
+            cur_len += d->payload_len;
+            if (!(d->flags & UVHTTP_WS_FLAG_FIN)) continue;
+            cur = 0;
+            if (closed || ((flags & UVHTTP_WS_ANSWER_SERVER_SEND) && cur_len == 0)) continue;
+            const uint64_t hdr = (cur_len <= 125 ? 2u : cur_len <= 65535 ? 4u : 10u) + (masked ? 4u : 0u);
+            if (pass == 1) {
+                uint8_t* o = out + bytes;
+                const uint32_t key = masked ? mask_keys[n] : 0u;
+                const int op = (flags & UVHTTP_WS_ANSWER_SERVER_SEND) ? UVHTTP_WS_OPCODE_TEXT : cur_op;
+                uint64_t h = 2;
+                o[0] = (uint8_t)(0x80u | (unsigned)op);
+                if (cur_len <= 125) {
+                    o[1] = (uint8_t)cur_len;
+                } else if (cur_len <= 65535) {
+                    o[1] = 126;
+                    o[2] = (uint8_t)(cur_len >> 8);
+                    o[3] = (uint8_t)cur_len;
+                    h = 4;
+                } else {
+                    o[1] = 127;
+                    for (int k = 0; k < 8; ++k) o[2 + k] = (uint8_t)(cur_len >> (8 * (7 - k)));
+                    h = 10;
+                }
+                if (masked) {
+                    o[1] |= 0x80u;
+                    for (int k = 0; k < 4; ++k) o[h + k] = (uint8_t)(key >> (8 * k));
+                }
+                echo_gather(o + hdr, wire, desc, lo, f, carry, carried ? carry_len : 0, key);
+                out_off[n] = bytes;
+            }
+            n++;
+            bytes += hdr + cur_len;
+        }
+        if (!cur || cur_len == 0) {
+            cur = 0;
+            cur_len = 0;
+        }
+        if (pass == 0) {
+            r->n_answers = (uint32_t)n;
+            r->n_replies = (uint32_t)n_rep;
+            r->out_len = bytes;
+            r->open_len = cur_len;
+            if (n > max_answers || bytes > out_cap || (open != NULL && cur_len > open_cap)) {
+                r->status = UVHTTP_WS_ECHO_ERR_CAPACITY;
+                if (q != NULL) q->status = UVHTTP_WS_REPLY_ERR_CAPACITY; /* closed stays, the rest 0 */
+                return 0;
+            }
+            if (q != NULL) {
+                q->n_replies = (uint32_t)n_rep;
+                q->out_len = rep_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)rep_bytes;
+            }
+            r->open_opcode = (uint8_t)(cur ? cur_op : 0);
+        } else {
+            for (uint64_t j = n; j <= max_answers; ++j) out_off[j] = bytes;
+            if (cur && open != NULL && n_delivered != 0)
+                echo_gather(open, wire, desc, lo, (uint64_t)first_frame + n_delivered - 1, carry,
+                            carried ? carry_len : 0, 0u);
+            else if (cur && open != NULL)
+                memcpy(open, carry, (size_t)carry_len);
+        }
+    }
+    return 0;
+}
+
 /* ---- relay of data messages: the room server's frames of a whole decoded batch -------------- */
 /* The host twin of uvhttp_ws_gpu_relay_messages_streams and the statement of its rules
  * (include/uvhttp_ws_amd.h): every connection's frames are what uvhttp_ws_echo_messages makes of
