@@ -30,35 +30,18 @@ $(BUILD)/ws_gpu.o: uvhttp_amd/csrc/ws_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_I
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-# UTF-8 validation of TEXT messages: no environment switches, so one object serves both libraries
-$(BUILD)/utf8_gpu.o: uvhttp_amd/csrc/utf8_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT) $(UTF8_RULES)
+# the stages after a decode (UTF-8 of messages and of frames, control replies, echo / relay /
+# answers, the server's CLOSE frames, fail points): no environment switches, so one object each
+# serves both libraries
+STAGES := utf8_gpu utf8_frames_gpu ws_replies_gpu ws_echo_gpu ws_close_gpu ws_fail_gpu
+STAGE_OBJS := $(STAGES:%=$(BUILD)/%.o)
+WS_SCAN := uvhttp_amd/csrc/ws_scan.h
+
+$(STAGE_OBJS): $(BUILD)/%.o: uvhttp_amd/csrc/%.hip include/uvhttp_ws_amd.h $(ENGINE_INT) $(WS_SCAN)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-# ... of TEXT frames after an in-place or stream decode: likewise one object for both
-$(BUILD)/utf8_frames_gpu.o: uvhttp_amd/csrc/utf8_frames_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT) $(UTF8_RULES)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-# control replies (PONG / CLOSE echo) after a decode: likewise one object for both
-$(BUILD)/ws_replies_gpu.o: uvhttp_amd/csrc/ws_replies_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-# the echo of data messages after a decode: likewise one object for both
-$(BUILD)/ws_echo_gpu.o: uvhttp_amd/csrc/ws_echo_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-# the server's own CLOSE frames (1002 / 1007) after a decode: likewise one object for both
-$(BUILD)/ws_close_gpu.o: uvhttp_amd/csrc/ws_close_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-
-# the fail points (cut a connection at its first violation) after a decode: likewise one object for both
-$(BUILD)/ws_fail_gpu.o: uvhttp_amd/csrc/ws_fail_gpu.hip include/uvhttp_ws_amd.h $(ENGINE_INT)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+$(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o: $(UTF8_RULES)
 
 $(BUILD)/tls_gpu.o: uvhttp_amd/csrc/tls_gpu.hip include/uvhttp_tls_amd.h $(DEVICE_GUARD)
 	@mkdir -p $(BUILD)
@@ -93,12 +76,12 @@ $(BUILD)/ws_batcher_group.o: uvhttp_amd/csrc/ws_batcher_group.cpp include/uvhttp
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -fPIC -std=c++17 -Iinclude -Wall -Wextra -Werror -c -o $@ $<
 
-$(LIB): $(BUILD)/ws_gpu.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/ws_fail_gpu.o $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
+$(LIB): $(BUILD)/ws_gpu.o $(STAGE_OBJS) $(BUILD)/tls_gpu.o $(BUILD)/ws_batcher.o $(BUILD)/ws_host.o \
         $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
-$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(BUILD)/utf8_gpu.o $(BUILD)/utf8_frames_gpu.o $(BUILD)/ws_replies_gpu.o $(BUILD)/ws_echo_gpu.o $(BUILD)/ws_close_gpu.o $(BUILD)/ws_fail_gpu.o $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
+$(TESTLIB): $(BUILD)/ws_gpu_exp.o $(STAGE_OBJS) $(BUILD)/tls_gpu_exp.o $(BUILD)/ws_batcher_testhooks.o $(BUILD)/ws_host_exp.o \
             $(BUILD)/ws_batcher_group.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
@@ -111,26 +94,13 @@ oracle:
 ctests: $(LIB) oracle tests/c/_build/close_check tests/c/_build/fail_check tests/c/_build/answer_check
 	$(MAKE) -C tests/c
 
-# the server's own CLOSE frames (ws_host.c: uvhttp_ws_close_frames) under ASan/UBSan, in a program
-# of its own (tests/c/close_check.c, run by tests/test_close_frames_host.py)
-tests/c/_build/close_check: tests/c/close_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
+# ws_host.c's close frames, fail points and answers under ASan/UBSan, each in a program of its
+# own (tests/c/NAME_check.c, run by tests/test_close_frames_host.py, test_fail_points_host.py and
+# test_answer_host.py)
+tests/c/_build/%_check: tests/c/%_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
 	@mkdir -p tests/c/_build
 	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
-	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/close_check.c uvhttp_amd/csrc/ws_host.c
-
-# the fail points (ws_host.c: uvhttp_ws_fail_points) under ASan/UBSan, likewise
-# (tests/c/fail_check.c, run by tests/test_fail_points_host.py)
-tests/c/_build/fail_check: tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
-	@mkdir -p tests/c/_build
-	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
-	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/fail_check.c uvhttp_amd/csrc/ws_host.c
-
-# the answers (ws_host.c: uvhttp_ws_answer_messages) under ASan/UBSan, likewise
-# (tests/c/answer_check.c, run by tests/test_answer_host.py)
-tests/c/_build/answer_check: tests/c/answer_check.c uvhttp_amd/csrc/ws_host.c include/uvhttp_ws_amd.h
-	@mkdir -p tests/c/_build
-	$(CC) -std=gnu11 -Wall -Wextra -Werror -Iinclude -O1 -g -fno-omit-frame-pointer \
-	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/c/answer_check.c uvhttp_amd/csrc/ws_host.c
+	  -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $< uvhttp_amd/csrc/ws_host.c
 
 # measurement tools run on the GPU box (PCIe ceilings beside the live-shape e2e)
 probes: tools/bin/pcie_probe tools/bin/copy_probe
@@ -144,16 +114,11 @@ tools/bin/copy_probe: tools/copy_probe.cpp $(BUILD)/ws_host.o
 	@mkdir -p tools/bin
 	g++ -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Iinclude -o $@ $^ -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib
 
-asm: uvhttp_amd/csrc/ws_gpu.hip uvhttp_amd/csrc/tls_gpu.hip uvhttp_amd/csrc/utf8_gpu.hip uvhttp_amd/csrc/utf8_frames_gpu.hip uvhttp_amd/csrc/ws_replies_gpu.hip uvhttp_amd/csrc/ws_echo_gpu.hip uvhttp_amd/csrc/ws_close_gpu.hip uvhttp_amd/csrc/ws_fail_gpu.hip
+asm:
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_gpu.s uvhttp_amd/csrc/ws_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/tls_gpu.s uvhttp_amd/csrc/tls_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/utf8_gpu.s uvhttp_amd/csrc/utf8_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/utf8_frames_gpu.s uvhttp_amd/csrc/utf8_frames_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_replies_gpu.s uvhttp_amd/csrc/ws_replies_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_echo_gpu.s uvhttp_amd/csrc/ws_echo_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_close_gpu.s uvhttp_amd/csrc/ws_close_gpu.hip
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/ws_fail_gpu.s uvhttp_amd/csrc/ws_fail_gpu.hip
+	set -e; for f in ws_gpu tls_gpu $(STAGES); do \
+	  $(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument --cuda-device-only -S -o $(BUILD)/$$f.s uvhttp_amd/csrc/$$f.hip; \
+	done
 
 clean:
 	rm -rf $(BUILD) uvhttp_amd/lib

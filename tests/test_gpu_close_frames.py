@@ -155,7 +155,9 @@ def _failing(n, which):
 
 
 @pytest.mark.parametrize("who", ["none", "one", "first", "last", "all"])
-@pytest.mark.parametrize("n", [255, 256, 257, 513])
+# (the last two: more than 64 and more than 256 block aggregates, so the top scan carries across a
+# wave boundary, and every lane of it folds a run of more than one aggregate)
+@pytest.mark.parametrize("n", [255, 256, 257, 513, 64 * 256 + 1, 256 * 256 + 1])
 def test_connections_across_scan_blocks(torch, eng, n, who):
     which = {"none": [], "one": [n // 2], "first": [0], "last": [n - 1], "all": list(range(n))}[who]
     ref = _check(torch, eng, _failing(n, which), n, twin=who != "all")

@@ -226,7 +226,10 @@ def test_bad_payload_range(torch, eng):
 
 # ---- scan boundaries ---------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1, 2 * SCAN_BLOCK + 1])
+# (the last two: more than 64 and more than 256 block aggregates, so the top scan of the head marks
+# carries across a wave boundary, and every lane of it folds a run of more than one aggregate)
+@pytest.mark.parametrize("n", [SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1, 2 * SCAN_BLOCK + 1,
+                               64 * SCAN_BLOCK + 1, 256 * SCAN_BLOCK + 1])
 @pytest.mark.parametrize("mode", ["none", "one", "ends", "all"])
 def test_scan_boundaries(torch, eng, n, mode):
     """n descriptors exactly (max_frames = n) over three connections, the middle one straddling

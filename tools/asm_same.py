@@ -7,7 +7,8 @@ revision's and the tree's:
 
 A function's text is everything from its label to its end marker.  Two things that move when a
 kernel is added beside it are taken out before comparing: the function's ordinal in the
-compiler's block labels (.LBB12_3, "Header=BB12_3"), and the __hip_cuid lines.  Nothing else is
+compiler's block labels (.LBB12_3, "Header=BB12_3") with the padding between such a label and its
+comment, which follows the label's length, and the __hip_cuid lines.  Nothing else is
 normalised: one different instruction, register or operand is a difference.  `--as OLD=NEW` pairs a
 function that was renamed (a kernel that became a template instance), its own name replaced in its
 text.  One line per function: SAME, DIFF (with the first differing lines), GONE or NEW; exit
@@ -28,7 +29,8 @@ def functions(path):
             continue
         if cur is None or "__hip_cuid" in line:
             continue
-        out[cur].append(re.sub(r"BB\d+_(?=\d)", "BB_", line))
+        line = re.sub(r"BB\d+_(?=\d)", "BB_", line)
+        out[cur].append(re.sub(r"^(\.LBB_\d+:) +;", r"\1 ;", line))
         if line.startswith(".Lfunc_end"):
             out[cur][-1] = ".Lfunc_end\n"
             cur = None

@@ -10,8 +10,7 @@
 //                 state) and a head mark at its first delivered descriptor
 //   k_fu_reduce   one lane per descriptor: the frame's effect on the connection's message state
 //                 as a 64-bit element (below), and the workgroup's aggregate
-//   k_fu_top      one workgroup: the aggregates' inclusive prefixes (every lane folds a run of
-//                 them, one scan over the runs)
+//   k_scan_top    one workgroup: the aggregates' inclusive prefixes (ws_scan.h)
 //   k_fu_apply    one lane per descriptor: the state carried into the frame (is it text, and the
 //                 up to three bytes before its first byte) and its connection from the scan.
 //                 Everything a carry can decide is judged here: the frame's first three bytes
@@ -19,7 +18,7 @@
 //                 CONTINUATION included), frames of up to three bytes whole, bad ranges and
 //                 CLOSE reasons.  A TEXT frame longer than three bytes is flagged as a segment
 //                 [payload_off + 3, payload end) for the payload pass
-//   k_fu_top      (sums: segments | text frames << 32) and k_fu_segs: the flagged segments
+//   k_scan_top    (sums: segments | text frames << 32) and k_fu_segs: the flagged segments
 //                 compacted into an ascending table (start, end, frame | connection << 32), and
 //                 every connection's text frames as the running count at its last frame minus
 //                 the count before its first (no atomics: in place all frames share a connection)
@@ -55,17 +54,15 @@
 #include "utf8_rules.h"
 #include "uvhttp_ws_amd.h"
 #include "ws_engine_int.h"
+#include "ws_scan.h"
 
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBlock = 256;  // the scan block: descriptors per workgroup
-constexpr int kWaves = kBlock / 64;
 constexpr int kVpt = 4;                              // k_fu_tiles: 16-byte vectors per lane
 constexpr uint64_t kWaveBytes = 64ull * 16 * kVpt;   // a wave's contiguous share: 4 KiB
 constexpr uint64_t kTileBytes = kWaveBytes * kWaves; // a workgroup's: 16 KiB
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kHigh = 0x80808080u;
 
 constexpr uint64_t kStBytes = 0xFFFFFFull;
@@ -115,44 +112,10 @@ struct StateOp {
     }
 };
 
-// two 32-bit counts in one word (neither can carry: at most 2^28 descriptors)
-struct AddOp {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-
-// inclusive scan over the workgroup's kBlock lanes; *total = all of them.  Every lane calls it.
-template <typename T, typename Op>
-__device__ __forceinline__ T block_scan(T v, Op op, T identity, T* s_wave, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d);
-        if (lane >= d) v = op(o, v);
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[w] = v;
-    __syncthreads();
-    T pre = identity, tot = identity;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) pre = op(pre, s_wave[k]);
-        tot = op(tot, s_wave[k]);
-    }
-    *total = tot;
-    return op(pre, v);
-}
-
-__device__ __forceinline__ bool range_ok(const FuArgs& a, uint64_t off, uint64_t len) {
-    return len <= a.wire_len && off <= a.wire_len - len;
-}
-
-// connection s's judged descriptors [ff, ff + nd), inside [0, max_frames)
-struct FuRange {
-    uint32_t ff, nd;
-};
-
-__device__ __forceinline__ FuRange conn_range(const FuArgs& a, uint32_t s) {
-    FuRange r;
+// connection s's judged descriptors, inside [0, max_frames).  Not call_failed: after ERR_DEVICE
+// the delivered frames are still judged (include/uvhttp_ws_amd.h, validate_utf8_streams)
+__device__ __forceinline__ Range conn_range(const FuArgs& a, uint32_t s) {
+    Range r;
     if (!a.results) {
         r.ff = 0;
         r.nd = a.bsum->n_delivered;
@@ -162,9 +125,7 @@ __device__ __forceinline__ FuRange conn_range(const FuArgs& a, uint32_t s) {
         r.nd = q.n_delivered;
         if (q.first_status == UVHTTP_WS_FRAME_ERR_CAPACITY || q.first_status == UVHTTP_WS_FRAME_ERR_LAYOUT) r.nd = 0;
     }
-    if (r.ff >= a.max_frames) r.nd = 0;
-    else if (r.nd > a.max_frames - r.ff) r.nd = a.max_frames - r.ff;
-    return r;
+    return clamp_range(r, a.max_frames);
 }
 
 // the state carried into connection s: a constant head element
@@ -200,7 +161,7 @@ __device__ __forceinline__ uint64_t frame_elem(const FuArgs& a, uint32_t f) {
         } else {
             const uint64_t len = d.payload_len;
             uint32_t k = 0, n = 0;
-            if (range_ok(a, d.payload_off, len)) {
+            if (range_ok(a.wire_len, d.payload_off, len)) {
                 k = len < 3 ? (uint32_t)len : 3u;
                 n = tail_bytes(a, d.payload_off, len, k);
             }
@@ -232,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void k_fu_conns(FuArgs a) {
     a.tbeg[s] = 0;
     a.tend[s] = 0;
     a.open[s] = (uint32_t)conn_seed(a, (uint32_t)s);
-    const FuRange r = conn_range(a, (uint32_t)s);
+    const Range r = conn_range(a, (uint32_t)s);
     if (r.nd) a.marks[r.ff] = (uint32_t)s + 1;
 }
 
@@ -245,31 +206,8 @@ __global__ __launch_bounds__(kBlock) void k_fu_reduce(FuArgs a) {
         a.elem[f] = e;
     }
     uint64_t tot;
-    (void)block_scan(e, StateOp(), (uint64_t)0, s_wave, &tot);
+    (void)block_scan(e, StateOp(), 0, s_wave, &tot);
     if (threadIdx.x == 0) a.agg1[blockIdx.x] = tot;
-}
-
-// one workgroup: agg[0, n) -> inclusive prefixes.  Every lane folds its own run of entries, the
-// runs' totals are scanned once, and the lane writes its run back with the prefix in front.
-template <typename Op>
-__global__ __launch_bounds__(kBlock) void k_fu_top(uint64_t* agg, uint32_t n) {
-    __shared__ uint64_t s_wave[kWaves];
-    const uint32_t per = (n + kBlock - 1) / kBlock;
-    const uint64_t lo = (uint64_t)threadIdx.x * per;
-    const uint64_t hi = lo + per < n ? lo + per : n;
-    uint64_t run = 0;
-    for (uint64_t i = lo; i < hi; ++i) run = Op()(run, agg[i]);
-    uint64_t tot;
-    const uint64_t inc = block_scan(run, Op(), (uint64_t)0, s_wave, &tot);
-    const uint64_t left = __shfl_up(inc, 1);  // the runs before this lane's
-    __shared__ uint64_t s_last[kWaves];
-    if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t acc = (threadIdx.x & 63) ? left : (threadIdx.x ? s_last[(threadIdx.x >> 6) - 1] : 0);
-    for (uint64_t i = lo; i < hi; ++i) {
-        acc = Op()(acc, agg[i]);
-        agg[i] = acc;
-    }
 }
 
 __device__ __forceinline__ void blame(uint32_t* first, uint32_t conn, uint32_t f) { atomicMin(&first[conn], f); }
@@ -284,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_fu_apply(FuArgs a) {
     const uint64_t e = live ? a.elem[f] : 0;
     const uint64_t pre = blockIdx.x ? a.agg1[blockIdx.x - 1] : 0;
     uint64_t tot;
-    const uint64_t inc = StateOp()(pre, block_scan(e, StateOp(), (uint64_t)0, s_wave, &tot));
+    const uint64_t inc = StateOp()(pre, block_scan(e, StateOp(), 0, s_wave, &tot));
     s_inc[threadIdx.x] = inc;
     __syncthreads();
     uint64_t carry = threadIdx.x ? s_inc[threadIdx.x - 1] : pre;
@@ -294,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_fu_apply(FuArgs a) {
     if (live && (inc & kStHead)) {
         conn = (uint32_t)(inc >> 32);
         if (conn < a.n_streams) {
-            const FuRange r = conn_range(a, conn);
+            const Range r = conn_range(a, conn);
             const uvhttp_ws_frame_desc_t& d = a.desc[f];
             if (f >= r.ff && f - r.ff < r.nd && d.status == UVHTTP_WS_FRAME_OK) {
                 judged = true;
@@ -306,7 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_fu_apply(FuArgs a) {
                 const uint32_t mop = op == 0 ? (uint32_t)(carry >> kStOpShift) & 3u : op;
                 if (op <= 2 && mop == 1) {
                     text = true;
-                    if (!range_ok(a, off, len)) {
+                    if (!range_ok(a.wire_len, off, len)) {
                         blame(a.first_bad, conn, (uint32_t)f);
                     } else {
                         const uint32_t cb = op == 0 ? (uint32_t)(carry & kStBytes) : 0u;
@@ -326,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void k_fu_apply(FuArgs a) {
                         seg = len > 3;
                     }
                 } else if (op == 8 && (a.flags & UVHTTP_WS_UTF8_CHECK_CLOSE) && len > 2) {
-                    if (!range_ok(a, off, len)) {
+                    if (!range_ok(a.wire_len, off, len)) {
                         blame(a.first_bad, conn, (uint32_t)f);
                     } else {
                         // a delivered control frame has at most 125 bytes
@@ -364,11 +302,11 @@ __global__ __launch_bounds__(kBlock) void k_fu_segs(FuArgs a) {
     const uint64_t info = f < a.max_frames ? a.elem[f] : 0;
     const uint64_t mine = ((info & kInfoSeg) ? 1ull : 0ull) | ((info & kInfoText) ? 1ull << 32 : 0ull);
     uint64_t tot;
-    const uint64_t inc = (blockIdx.x ? a.agg2[blockIdx.x - 1] : 0ull) + block_scan(mine, AddOp(), (uint64_t)0, s_wave, &tot);
+    const uint64_t inc = (blockIdx.x ? a.agg2[blockIdx.x - 1] : 0ull) + block_scan(mine, AddOp(), 0, s_wave, &tot);
     if (info & kInfoJudged) {
         // the connection's text frames = the running count at its last frame - before its first
         const uint32_t conn = (uint32_t)(info >> 32);
-        const FuRange r = conn_range(a, conn);
+        const Range r = conn_range(a, conn);
         if (f == r.ff) a.tbeg[conn] = (uint32_t)((inc - mine) >> 32);
         if (f - r.ff == r.nd - 1) a.tend[conn] = (uint32_t)(inc >> 32);
     }
@@ -600,55 +538,46 @@ __global__ __launch_bounds__(kBlock) void k_fu_finish(FuArgs a) {
     }
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+void fu_carve(Carver& c, FuArgs& a, uint64_t nb) {
+    const uint64_t F = a.max_frames, S = a.n_streams;
+    a.elem = c.take<uint64_t>(F);
+    a.seg_start = c.take<uint64_t>(F);
+    a.seg_end = c.take<uint64_t>(F);
+    a.seg_fc = c.take<uint64_t>(F);
+    a.agg1 = c.take<uint64_t>(nb);
+    a.marks = c.take<uint32_t>(F);
+    a.agg2 = c.take<uint64_t>(nb);
+    a.first_inv = c.take<uint32_t>(S);
+    a.first_bad = c.take<uint32_t>(S);
+    a.tbeg = c.take<uint32_t>(S);
+    a.tend = c.take<uint32_t>(S);
+    a.open = c.take<uint32_t>(S);
+}
 
 int fu_run(uvhttp_ws_gpu_engine_t* e, FuArgs a, void* stream, const char* what) {
     static_assert(sizeof(uvhttp_ws_utf8_conn_verdict_t) == 16 && sizeof(uvhttp_ws_utf8_frames_summary_t) == 16, "ABI");
-    const uint64_t F = a.max_frames, S = a.n_streams;
-    const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
-    const uint64_t nb = blocks ? blocks : 1;
-    size_t off = 0;
-    const size_t o_elem = off;      off = align_up(off + F * 8);
-    const size_t o_start = off;     off = align_up(off + F * 8);
-    const size_t o_end = off;       off = align_up(off + F * 8);
-    const size_t o_fc = off;        off = align_up(off + F * 8);
-    const size_t o_agg1 = off;      off = align_up(off + nb * 8);
-    const size_t o_marks = off;     off = align_up(off + F * 4);
-    const size_t o_agg2 = off;      off = align_up(off + nb * 8);
-    const size_t o_inv = off;       off = align_up(off + S * 4);
-    const size_t o_bad = off;       off = align_up(off + S * 4);
-    const size_t o_tbeg = off;      off = align_up(off + S * 4);
-    const size_t o_tend = off;      off = align_up(off + S * 4);
-    const size_t o_open = off;      off = align_up(off + S * 4);
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.max_frames + kBlock - 1) / kBlock);
+    Carver count{nullptr};
+    fu_carve(count, a, blocks ? blocks : 1);
 
     hipStream_t s = (hipStream_t)stream;
     const int prev = uvws_call_enter(e, s);
-    char* mem = static_cast<char*>(uvws_utf8_scratch(e, off ? off : 256, s));
+    char* mem = static_cast<char*>(uvws_utf8_scratch(e, count.bytes(), s));
     if (!mem) {
         (void)uvws_call_leave(e, prev, what);
         return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "validate_utf8 frame scratch (a captured call must not grow it)");
     }
-    a.elem = reinterpret_cast<uint64_t*>(mem + o_elem);
-    a.seg_start = reinterpret_cast<uint64_t*>(mem + o_start);
-    a.seg_end = reinterpret_cast<uint64_t*>(mem + o_end);
-    a.seg_fc = reinterpret_cast<uint64_t*>(mem + o_fc);
-    a.agg1 = reinterpret_cast<uint64_t*>(mem + o_agg1);
-    a.marks = reinterpret_cast<uint32_t*>(mem + o_marks);
-    a.agg2 = reinterpret_cast<uint64_t*>(mem + o_agg2);
-    a.first_inv = reinterpret_cast<uint32_t*>(mem + o_inv);
-    a.first_bad = reinterpret_cast<uint32_t*>(mem + o_bad);
-    a.tbeg = reinterpret_cast<uint32_t*>(mem + o_tbeg);
-    a.tend = reinterpret_cast<uint32_t*>(mem + o_tend);
-    a.open = reinterpret_cast<uint32_t*>(mem + o_open);
+    Carver carve{mem};
+    fu_carve(carve, a, blocks ? blocks : 1);
 
-    const uint32_t grid_s = (uint32_t)((S + kBlock - 1) / kBlock);
+    const uint32_t grid_s = (uint32_t)(((uint64_t)a.n_streams + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_fu_init, dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
     if (grid_s) hipLaunchKernelGGL(k_fu_conns, dim3(grid_s), dim3(kBlock), 0, s, a);
     if (blocks && grid_s) {
         hipLaunchKernelGGL(k_fu_reduce, dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_fu_top<StateOp>), dim3(1), dim3(kBlock), 0, s, a.agg1, blocks);
+        hipLaunchKernelGGL((k_scan_top<StateOp>), dim3(1), dim3(kBlock), 0, s, a.agg1, a.agg1, blocks);
         hipLaunchKernelGGL(k_fu_apply, dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_fu_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg2, blocks);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg2, a.agg2, blocks);
         hipLaunchKernelGGL(k_fu_segs, dim3(blocks), dim3(kBlock), 0, s, a);
         const uint64_t tiles = (a.wire_len + kTileBytes - 1) / kTileBytes;
         engine_grid_chunks(e, tiles, [&](uint32_t grid, uint64_t tb) {

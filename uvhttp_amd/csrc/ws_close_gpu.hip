@@ -8,7 +8,7 @@
 //
 //   k_cl_size   one lane per connection: its code and frame bytes from its stream, result,
 //               verdict and reply result; the workgroup's closes (1002 and 1007) and bytes
-//   k_cl_top    both aggregates' inclusive prefixes (two workgroups)
+//   k_scan_top  both aggregates' inclusive prefixes (two workgroups; ws_scan.h)
 //   k_cl_emit   one lane per connection: the same code again, its frame index and byte offset
 //               from the scan, then the frame (at most 22 bytes, written by the lane), d_out_off,
 //               the run, the cleared runs of a 1007 connection, the 16-byte result; the first
@@ -20,11 +20,10 @@
 
 #include "uvhttp_ws_amd.h"
 #include "ws_engine_int.h"
+#include "ws_scan.h"
 
 namespace {
 
-constexpr int kBlock = 256;  // connections per workgroup
-constexpr int kWaves = kBlock / 64;
 constexpr uint32_t kReasonLen = 14;  // "protocol error"
 
 struct ClArgs {
@@ -51,27 +50,6 @@ struct ClArgs {
     uint32_t blocks;
 };
 
-// inclusive sum over the workgroup's kBlock lanes; *total = all of them.  Every lane calls it.
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* s_wave, uint64_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[w] = v;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) pre += s_wave[k];
-        tot += s_wave[k];
-    }
-    *total = tot;
-    return pre + v;
-}
-
 // connection s: the code it is closed with (0 = none), whether only the key is missing
 struct ClConn {
     uint32_t code;
@@ -84,8 +62,7 @@ __device__ __forceinline__ ClConn conn_close(const ClArgs& a, uint64_t s) {
     if (s >= a.n_streams) return c;
     if (a.enable && a.enable[s] == 0) return c;
     const int32_t fs = a.results[s].first_status;
-    if (fs == UVHTTP_WS_FRAME_ERR_CAPACITY || fs == UVHTTP_WS_FRAME_ERR_LAYOUT || fs == UVHTTP_WS_FRAME_ERR_DEVICE)
-        return c;
+    if (call_failed(fs)) return c;
     if (a.reply && a.reply[s].closed) return c;
     uint32_t code = 0;
     if (a.verdict && a.verdict[s].status == UVHTTP_WS_UTF8_INVALID) code = 1007;
@@ -110,28 +87,11 @@ __global__ __launch_bounds__(kBlock) void k_cl_size(ClArgs a, uint64_t tb) {
     const uint64_t b = tb + blockIdx.x;
     const ClConn c = conn_close(a, b * kBlock + threadIdx.x);
     uint64_t tc, tl;
-    (void)block_scan(count_word(c), s_wave, &tc);
-    (void)block_scan(c.len, s_wave, &tl);
+    (void)block_scan(count_word(c), AddOp(), 0, s_wave, &tc);
+    (void)block_scan(c.len, AddOp(), 0, s_wave, &tl);
     if (threadIdx.x == 0) {
         a.agg_cnt[b] = tc;
         a.agg_bytes[b] = tl;
-    }
-}
-
-// one workgroup per column: agg[0, n) -> inclusive prefixes, every lane folding a run of entries
-__global__ __launch_bounds__(kBlock) void k_cl_top(uint64_t* agg0, uint64_t* agg1, uint32_t n) {
-    __shared__ uint64_t s_wave[kWaves];
-    uint64_t* agg = blockIdx.x ? agg1 : agg0;
-    const uint32_t per = (n + kBlock - 1) / kBlock;
-    const uint64_t lo = (uint64_t)threadIdx.x * per;
-    const uint64_t hi = lo + per < n ? lo + per : n;
-    uint64_t run = 0;
-    for (uint64_t i = lo; i < hi; ++i) run += agg[i];
-    uint64_t tot;
-    uint64_t acc = block_scan(run, s_wave, &tot) - run;  // the runs before this lane's
-    for (uint64_t i = lo; i < hi; ++i) {
-        acc += agg[i];
-        agg[i] = acc;
     }
 }
 
@@ -141,8 +101,8 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit(ClArgs a, uint64_t tb) {
     const uint64_t s = b * kBlock + threadIdx.x;
     const ClConn c = conn_close(a, s);
     uint64_t tc, tl;
-    const uint64_t ic = (b ? a.agg_cnt[b - 1] : 0) + block_scan(count_word(c), s_wave, &tc);  // inclusive
-    const uint64_t il = (b ? a.agg_bytes[b - 1] : 0) + block_scan(c.len, s_wave, &tl);
+    const uint64_t ic = (b ? a.agg_cnt[b - 1] : 0) + block_scan(count_word(c), AddOp(), 0, s_wave, &tc);  // inclusive
+    const uint64_t il = (b ? a.agg_bytes[b - 1] : 0) + block_scan(c.len, AddOp(), 0, s_wave, &tl);
     const uint64_t all_cnt = a.agg_cnt[a.blocks - 1], all_bytes = a.agg_bytes[a.blocks - 1];
     const uint32_t n1002 = (uint32_t)(all_cnt >> 32), n1007 = (uint32_t)all_cnt;
     const bool fits = all_bytes <= a.out_cap;
@@ -201,7 +161,10 @@ __global__ __launch_bounds__(kBlock) void k_cl_emit(ClArgs a, uint64_t tb) {
     a.conn[s] = r;
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+void cl_carve(Carver& c, ClArgs& a) {
+    a.agg_cnt = c.take<uint64_t>(a.blocks);
+    a.agg_bytes = c.take<uint64_t>(a.blocks);
+}
 
 }  // namespace
 
@@ -257,18 +220,19 @@ extern "C" int uvhttp_ws_gpu_close_frames_streams(
         (void)hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), s);
         return uvws_call_leave(e, prev, "close_frames_streams launch");
     }
-    const size_t o_bytes = align_up(blocks * 8);
-    char* mem = static_cast<char*>(uvws_close_scratch(e, o_bytes + align_up(blocks * 8), s));
+    Carver count{nullptr};
+    cl_carve(count, a);
+    char* mem = static_cast<char*>(uvws_close_scratch(e, count.bytes(), s));
     if (!mem) {
         (void)uvws_call_leave(e, prev, "close_frames_streams launch");
         return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "close_frames scratch (a captured call must not grow it)");
     }
-    a.agg_cnt = reinterpret_cast<uint64_t*>(mem);
-    a.agg_bytes = reinterpret_cast<uint64_t*>(mem + o_bytes);
+    Carver carve{mem};
+    cl_carve(carve, a);
     engine_grid_chunks(e, blocks, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_cl_size, dim3(grid), dim3(kBlock), 0, s, a, tb);
     });
-    hipLaunchKernelGGL(k_cl_top, dim3(2), dim3(kBlock), 0, s, a.agg_cnt, a.agg_bytes, a.blocks);
+    hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(2), dim3(kBlock), 0, s, a.agg_cnt, a.agg_bytes, a.blocks);
     engine_grid_chunks(e, blocks, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_cl_emit, dim3(grid), dim3(kBlock), 0, s, a, tb);
     });

@@ -9,12 +9,12 @@
 //   k_echo_init     marks[f] = 0 per descriptor; the summary zeroed
 //   k_echo_conns    one lane per connection: its state word (enabled, NO_KEYS, NO_CARRY, carries
 //                   in), its scratch words, a head mark at its first considered descriptor
-//   k_echo_reduce / k_echo_top   the scan of the head marks (as the control replies')
+//   k_mark_reduce / k_scan_top   the scan of the head marks (ws_scan.h)
 //   k_echo_classify one lane per descriptor, 32 bytes read: its connection; a word — in range,
 //                   first / last of the range, a delivered data frame, start of a message, FIN;
 //                   first_close[connection] (atomicMin), bad[connection] for a payload outside
 //                   the wire.  The workgroup's data-payload bytes and its last message marker
-//   k_echo_top      both aggregates
+//   k_scan_top      both aggregates, one launch each
 //   k_echo_prefix   one lane per descriptor: dsum[f] = data-payload bytes before f (a message's
 //                   length is a difference of two of them plus its carry), and view[f] = the
 //                   message f belongs to: the nearest earlier start frame, or the head of the
@@ -23,13 +23,13 @@
 //                   is echoed (not after the first CLOSE, not empty under SERVER_SEND, connection
 //                   not bad) and sizes the frame; the lane of a range's last frame sizes the
 //                   message still open.  The workgroup's echoes and bytes
-//   k_echo_top, k_echo_creduce, k_echo_top   the totals: echoes, bytes, open bytes — the one set
+//   k_scan_top, k_echo_creduce, k_scan_top   the totals: echoes, bytes, open bytes — the one set
 //                   every writer goes by
 //   k_echo_offsets  one lane per descriptor: slot and offset from the scan; d_out_off[j] and the
 //                   echo's record (where its bytes come from), written by the FIN frame's lane;
 //                   the running totals before a connection's first frame and after its last
 //   k_echo_tail     d_out_off[n_echoes .. max_echoes] = the total (all 0 on capacity)
-//   k_echo_creduce / k_echo_top / k_echo_finish   one lane per connection: first_echo and
+//   k_echo_creduce / k_scan_top / k_echo_finish   one lane per connection: first_echo and
 //                   d_open_off as exclusive sums, the 32-byte result, the run, the open message's
 //                   record, the summary
 //   k_echo_emit     the hot path: P bytes read, H + P written.  One workgroup per 64 KiB tile of
@@ -61,9 +61,9 @@
 // is added lies between k_echo_size and the record writes:
 //
 //   k_echo_offsets  run once for the connections' counts and bytes only (cbeg .. bend)
-//   k_relay_hist / _hreduce / k_echo_top / k_relay_hscan / k_relay_scatter   per 8 bits of n_rooms:
+//   k_relay_hist / _hreduce / k_scan_top / k_relay_hscan / k_relay_scatter   per 8 bits of n_rooms:
 //                   the connections sorted by (min(room, n_rooms), index), see "the relay's order"
-//   k_relay_oreduce / k_echo_top x 2 / k_relay_obase   counts and bytes scanned in that order:
+//   k_relay_oreduce / k_scan_top x 2 / k_relay_obase   counts and bytes scanned in that order:
 //                   every connection's first slot and offset, and the sums by place for the rooms
 //   k_echo_offsets  again: each record, d_out_off[j] and the tile map at the connection's base
 //   k_relay_rooms   one lane per room: two searches over the sorted keys, d_rooms[r]
@@ -84,7 +84,7 @@
 //                    CLOSE unless the flag says so, connection not bad) and sizes the reply: 2
 //                    header bytes, 4 more when masked, the payload.  A third aggregate, replies
 //                    << 35 | their payload bytes, for the per-connection reply counts
-//   k_echo_top       ... its prefixes
+//   k_scan_top       ... its prefixes
 //   k_echo_offsets   the reply's record on its own lane: b0 = 0x8A or 0x88, one = 1, g = fend = f,
 //                    src0 = the control frame's payload_off; rbeg / rend per connection
 //   k_echo_finish    the answer result (closed, n_replies), the optional reply table that
@@ -103,12 +103,10 @@
 
 #include "uvhttp_ws_amd.h"
 #include "ws_engine_int.h"
+#include "ws_scan.h"
 
 namespace {
 
-constexpr int kBlock = 256;  // the scan block: descriptors (or connections) per workgroup
-constexpr int kWaves = kBlock / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr int kBatch = 4;     // vectors a lane of the emit handles side by side
 constexpr int kBatches = 4;   // ... this many times
 constexpr int kVecPerLane = kBatch * kBatches;
@@ -257,46 +255,9 @@ struct AnArgs : EcArgs {
 // replies << 35 | payload bytes: at most 2^28 replies of at most 125 bytes
 constexpr int kRepShift = 35;
 
-struct LastOp {  // the later mark
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return b ? b : a; }
-};
-struct AddOp {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-
-// inclusive scan over the workgroup's kBlock lanes; *total = all of them.  Every lane calls it.
-template <typename Op>
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, Op op, uint64_t* s_wave, uint64_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v = op(o, v);
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[w] = v;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) pre = op(pre, s_wave[k]);
-        tot = op(tot, s_wave[k]);
-    }
-    *total = tot;
-    return op(pre, v);
-}
-
-__device__ __forceinline__ bool range_ok(uint64_t limit, uint64_t off, uint64_t len) {
-    return len <= limit && off <= limit - len;
-}
-
-// connection s's considered descriptors [ff, ff + nd), inside [0, max_frames)
-struct EcRange {
-    uint32_t ff, nd;
-};
-
-__device__ __forceinline__ EcRange conn_range(const EcArgs& a, uint32_t s) {
-    EcRange r;
+// connection s's considered descriptors, inside [0, max_frames)
+__device__ __forceinline__ Range conn_range(const EcArgs& a, uint32_t s) {
+    Range r;
     if (!a.results) {
         r.ff = 0;
         r.nd = a.bsum->n_delivered;
@@ -304,13 +265,9 @@ __device__ __forceinline__ EcRange conn_range(const EcArgs& a, uint32_t s) {
         const uvhttp_ws_stream_result_t& q = a.results[s];
         r.ff = q.first_frame;
         r.nd = q.n_delivered;
-        if (q.first_status == UVHTTP_WS_FRAME_ERR_CAPACITY || q.first_status == UVHTTP_WS_FRAME_ERR_LAYOUT ||
-            q.first_status == UVHTTP_WS_FRAME_ERR_DEVICE)
-            r.nd = 0;
+        if (call_failed(q.first_status)) r.nd = 0;
     }
-    if (r.ff >= a.max_frames) r.nd = 0;
-    else if (r.nd > a.max_frames - r.ff) r.nd = a.max_frames - r.ff;
-    return r;
+    return clamp_range(r, a.max_frames);
 }
 
 __device__ __forceinline__ bool conn_server(const EcArgs& a, uint32_t s) {
@@ -414,44 +371,12 @@ __global__ __launch_bounds__(kBlock) void k_echo_conns(A a) {
         a.sidx[0][s] = (uint32_t)s;
     }
     a.cstate[s] = st;
-    const EcRange r = conn_range(a, (uint32_t)s);
+    const Range r = conn_range(a, (uint32_t)s);
     if (r.nd) a.marks[r.ff] = (uint32_t)s + 1;
     // a connection that considers no frame passes its carry through
     const bool through = !r.nd && (st & kCCarry);
     a.olen[s] = through ? pend : 0;
     a.omark[s] = through ? marker(0, kMsgCarryOnly) : 0;
-}
-
-__global__ __launch_bounds__(kBlock) void k_echo_reduce(EcArgs a) {
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t m = f < a.max_frames ? a.marks[f] : 0;
-    uint64_t tot;
-    (void)block_scan(m, LastOp(), s_wave, &tot);
-    if (threadIdx.x == 0) a.agg_mark[blockIdx.x] = tot;
-}
-
-// one workgroup: agg[0, n) -> inclusive prefixes.  Every lane folds its own run of entries, the
-// runs' totals are scanned once, and the lane writes its run back with the prefix in front.
-template <typename Op>
-__global__ __launch_bounds__(kBlock) void k_echo_top(uint64_t* agg, uint32_t n) {
-    __shared__ uint64_t s_wave[kWaves];
-    __shared__ uint64_t s_last[kWaves];
-    const uint32_t per = (n + kBlock - 1) / kBlock;
-    const uint64_t lo = (uint64_t)threadIdx.x * per;
-    const uint64_t hi = lo + per < n ? lo + per : n;
-    uint64_t run = 0;
-    for (uint64_t i = lo; i < hi; ++i) run = Op()(run, agg[i]);
-    uint64_t tot;
-    const uint64_t inc = block_scan(run, Op(), s_wave, &tot);
-    const uint64_t left = __shfl_up(inc, 1);  // the runs before this lane's
-    if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t acc = (threadIdx.x & 63) ? left : (threadIdx.x ? s_last[(threadIdx.x >> 6) - 1] : 0);
-    for (uint64_t i = lo; i < hi; ++i) {
-        acc = Op()(acc, agg[i]);
-        agg[i] = acc;
-    }
 }
 
 // what frame f posts for the frames after it: a FIN data frame ends the message, a start frame
@@ -469,14 +394,11 @@ __global__ __launch_bounds__(kBlock) void k_echo_classify(A a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = f < a.max_frames;
-    const uint64_t m = live ? a.marks[f] : 0;
-    const uint64_t pre = blockIdx.x ? a.agg_mark[blockIdx.x - 1] : 0;
-    uint64_t tot;
-    const uint64_t head = LastOp()(pre, block_scan(m, LastOp(), s_wave, &tot));
+    const uint64_t head = head_mark(a.marks, a.max_frames, a.agg_mark, blockIdx.x, s_wave);
     uint64_t e = 0, plen = 0;
     if (live && head != 0 && head - 1 < a.n_streams) {
         const uint32_t conn = (uint32_t)(head - 1);
-        const EcRange r = conn_range(a, conn);
+        const Range r = conn_range(a, conn);
         if (f >= r.ff && f - r.ff < r.nd) {
             const uint32_t cs = a.cstate[conn];
             e = kIn | ((uint64_t)conn << 32) | (f == r.ff ? kFirst : 0) | (f - r.ff == r.nd - 1 ? kLast : 0);
@@ -509,8 +431,8 @@ __global__ __launch_bounds__(kBlock) void k_echo_classify(A a) {
     }
     if (live) a.elem[f] = e;
     uint64_t tot_d, tot_p;
-    (void)block_scan(plen, AddOp(), s_wave, &tot_d);
-    (void)block_scan(posted_of(e, f), LastOp(), s_wave, &tot_p);
+    (void)block_scan(plen, AddOp(), 0, s_wave, &tot_d);
+    (void)block_scan(posted_of(e, f), LastOp(), 0, s_wave, &tot_p);
     if (threadIdx.x == 0) {
         a.agg_d[blockIdx.x] = tot_d;
         a.agg_post[blockIdx.x] = tot_p;
@@ -525,8 +447,8 @@ __global__ __launch_bounds__(kBlock) void k_echo_prefix(EcArgs a) {
     const uint64_t e = live ? a.elem[f] : 0;
     const uint64_t plen = (e & kData) ? a.desc[f].payload_len : 0;
     uint64_t tot;
-    const uint64_t inc_d = (blockIdx.x ? a.agg_d[blockIdx.x - 1] : 0) + block_scan(plen, AddOp(), s_wave, &tot);
-    s_inc[threadIdx.x] = block_scan(posted_of(e, f), LastOp(), s_wave, &tot);
+    const uint64_t inc_d = (blockIdx.x ? a.agg_d[blockIdx.x - 1] : 0) + block_scan(plen, AddOp(), 0, s_wave, &tot);
+    s_inc[threadIdx.x] = block_scan(posted_of(e, f), LastOp(), 0, s_wave, &tot);
     __syncthreads();
     const uint64_t before = LastOp()(blockIdx.x ? a.agg_post[blockIdx.x - 1] : 0, threadIdx.x ? s_inc[threadIdx.x - 1] : 0);
     if (!live) return;
@@ -587,15 +509,15 @@ __global__ __launch_bounds__(kBlock) void k_echo_size(A a) {
     uint64_t tot_c, tot_b;
     bool counts = (e & kEcho) != 0;
     if constexpr (A::kAnswer) counts = (e & (kEcho | kReply)) != 0;
-    (void)block_scan(counts ? 1 : 0, AddOp(), s_wave, &tot_c);
-    (void)block_scan(bytes, AddOp(), s_wave, &tot_b);
+    (void)block_scan(counts ? 1 : 0, AddOp(), 0, s_wave, &tot_c);
+    (void)block_scan(bytes, AddOp(), 0, s_wave, &tot_b);
     if (threadIdx.x == 0) {
         a.agg_cnt[blockIdx.x] = tot_c;
         a.agg_bytes[blockIdx.x] = tot_b;
     }
     if constexpr (A::kAnswer) {
         uint64_t tot_r;
-        (void)block_scan((e & kReply) ? (1ull << kRepShift) | ctl_len(e) : 0, AddOp(), s_wave, &tot_r);
+        (void)block_scan((e & kReply) ? (1ull << kRepShift) | ctl_len(e) : 0, AddOp(), 0, s_wave, &tot_r);
         if (threadIdx.x == 0) a.agg_rep[blockIdx.x] = tot_r;
     }
 }
@@ -631,8 +553,8 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
         }
     }
     uint64_t tot;
-    const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + block_scan(echo ? 1 : 0, AddOp(), s_wave, &tot);
-    const uint64_t bytes = (blockIdx.x ? a.agg_bytes[blockIdx.x - 1] : 0) + block_scan(mine, AddOp(), s_wave, &tot);
+    const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + block_scan(echo ? 1 : 0, AddOp(), 0, s_wave, &tot);
+    const uint64_t bytes = (blockIdx.x ? a.agg_bytes[blockIdx.x - 1] : 0) + block_scan(mine, AddOp(), 0, s_wave, &tot);
     bool bounds = (e & kIn) != 0;
     if constexpr (A::kRelay) bounds = bounds && a.count_only;  // (the relay's second run reads them)
     if (bounds) {
@@ -647,7 +569,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_offsets(A a) {
     }
     if constexpr (A::kAnswer) {
         const uint64_t mine_r = reply ? (1ull << kRepShift) | len : 0;
-        const uint64_t rep = (blockIdx.x ? a.agg_rep[blockIdx.x - 1] : 0) + block_scan(mine_r, AddOp(), s_wave, &tot);
+        const uint64_t rep = (blockIdx.x ? a.agg_rep[blockIdx.x - 1] : 0) + block_scan(mine_r, AddOp(), 0, s_wave, &tot);
         if (e & kIn) {
             if (e & kFirst) a.rbeg[conn] = rep - mine_r;
             if (e & kLast) a.rend[conn] = rep;
@@ -730,7 +652,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_creduce(EcArgs a, int which) {
     uint64_t n = 0;
     if (s < a.n_streams) n = which ? a.olen[s] : (uint64_t)(a.cend[s] - a.cbeg[s]);
     uint64_t tot;
-    (void)block_scan(n, AddOp(), s_wave, &tot);
+    (void)block_scan(n, AddOp(), 0, s_wave, &tot);
     if (threadIdx.x == 0) (which ? a.agg_co : a.agg_cn)[blockIdx.x] = tot;
 }
 
@@ -742,8 +664,8 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(A a) {
     const uint32_t n = live ? a.cend[s] - a.cbeg[s] : 0;
     const uint64_t ol = live ? a.olen[s] : 0;
     uint64_t tot, inc_n = 0;  // (the relay has every connection's first slot already)
-    if constexpr (!A::kRelay) inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
-    const uint64_t inc_o = (blockIdx.x ? a.agg_co[blockIdx.x - 1] : 0) + block_scan(ol, AddOp(), s_wave, &tot);
+    if constexpr (!A::kRelay) inc_n = (blockIdx.x ? a.agg_cn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), 0, s_wave, &tot);
+    const uint64_t inc_o = (blockIdx.x ? a.agg_co[blockIdx.x - 1] : 0) + block_scan(ol, AddOp(), 0, s_wave, &tot);
     const EcTotals t = totals(a);
     [[maybe_unused]] bool closed = false;
     if (live) {
@@ -852,7 +774,7 @@ __global__ __launch_bounds__(kBlock) void k_echo_finish(A a) {
 // The connections sorted by (min(room, n_rooms), index): a least-significant-digit radix sort of
 // 8 bits a pass over the bits n_rooms needs.  A pass is k_relay_hist (a workgroup's 256 keys ->
 // its count per digit, stored digit-major, so that one exclusive scan of the whole table gives
-// every (digit, workgroup) its base), the scan (k_relay_hreduce, k_echo_top, k_relay_hscan) and
+// every (digit, workgroup) its base), the scan (k_relay_hreduce, k_scan_top, k_relay_hscan) and
 // k_relay_scatter, which ranks a key among the equal digits before it in its workgroup: stable,
 // so equal rooms keep index order.  Every kernel takes the first workgroup of its piece.
 
@@ -871,7 +793,7 @@ __global__ __launch_bounds__(kBlock) void k_relay_hreduce(RlArgs a, uint64_t bas
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t b = base + blockIdx.x;
     uint64_t tot;
-    (void)block_scan(a.hist[b * kBlock + threadIdx.x], AddOp(), s_wave, &tot);
+    (void)block_scan(a.hist[b * kBlock + threadIdx.x], AddOp(), 0, s_wave, &tot);
     if (threadIdx.x == 0) a.agg_h[b] = tot;
 }
 
@@ -880,7 +802,7 @@ __global__ __launch_bounds__(kBlock) void k_relay_hscan(RlArgs a, uint64_t base)
     const uint64_t b = base + blockIdx.x;
     const uint32_t v = a.hist[b * kBlock + threadIdx.x];
     uint64_t tot;
-    const uint64_t inc = (b ? a.agg_h[b - 1] : 0) + block_scan(v, AddOp(), s_wave, &tot);
+    const uint64_t inc = (b ? a.agg_h[b - 1] : 0) + block_scan(v, AddOp(), 0, s_wave, &tot);
     a.hist[b * kBlock + threadIdx.x] = (uint32_t)(inc - v);
 }
 
@@ -929,8 +851,8 @@ __global__ __launch_bounds__(kBlock) void k_relay_oreduce(RlArgs a, uint64_t bas
     uint32_t s;
     uint64_t n, bytes, tot_n, tot_b;
     place_sizes(a, b * kBlock + threadIdx.x, &s, &n, &bytes);
-    (void)block_scan(n, AddOp(), s_wave, &tot_n);
-    (void)block_scan(bytes, AddOp(), s_wave, &tot_b);
+    (void)block_scan(n, AddOp(), 0, s_wave, &tot_n);
+    (void)block_scan(bytes, AddOp(), 0, s_wave, &tot_b);
     if (threadIdx.x == 0) {
         a.agg_pc[b] = tot_n;
         a.agg_pb[b] = tot_b;
@@ -943,8 +865,8 @@ __global__ __launch_bounds__(kBlock) void k_relay_obase(RlArgs a, uint64_t base)
     uint32_t s;
     uint64_t n, bytes, tot;
     place_sizes(a, p, &s, &n, &bytes);
-    const uint64_t inc_n = (b ? a.agg_pc[b - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
-    const uint64_t inc_b = (b ? a.agg_pb[b - 1] : 0) + block_scan(bytes, AddOp(), s_wave, &tot);
+    const uint64_t inc_n = (b ? a.agg_pc[b - 1] : 0) + block_scan(n, AddOp(), 0, s_wave, &tot);
+    const uint64_t inc_b = (b ? a.agg_pb[b - 1] : 0) + block_scan(bytes, AddOp(), 0, s_wave, &tot);
     if (p >= a.n_streams) return;
     a.pcnt[p] = inc_n - n;
     a.pbytes[p] = inc_b - bytes;
@@ -1231,103 +1153,86 @@ __global__ __launch_bounds__(kBlock) void k_echo_emit(A a, uint64_t tile_base, u
     }
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+template <class A>
+void ec_carve(Carver& c, A& a, uint64_t nb, uint64_t ns, uint64_t tiles_out, uint64_t tiles_open) {
+    const uint64_t F = a.max_frames, S = a.n_streams;
+    a.elem = c.take<uint64_t>(F);
+    a.dsum = c.take<uint64_t>(F);
+    a.view = c.take<uint64_t>(F);
+    a.agg_mark = c.take<uint64_t>(nb);
+    a.agg_d = c.take<uint64_t>(nb);
+    a.agg_post = c.take<uint64_t>(nb);
+    a.agg_cnt = c.take<uint64_t>(nb);
+    a.agg_bytes = c.take<uint64_t>(nb);
+    a.agg_cn = c.take<uint64_t>(ns);
+    a.agg_co = c.take<uint64_t>(ns);
+    a.bbeg = c.take<uint64_t>(S);
+    a.bend = c.take<uint64_t>(S);
+    a.olen = c.take<uint64_t>(S);
+    a.omark = c.take<uint64_t>(S);
+    a.rec = c.take<EcRec>(a.max_echoes);
+    a.orec = c.take<EcRec>(S);
+    a.marks = c.take<uint32_t>(F);
+    a.tmap = c.take<uint32_t>(tiles_out + 1);
+    a.omap = c.take<uint32_t>(tiles_open + 1);
+    a.cstate = c.take<uint32_t>(S);
+    a.first_close = c.take<uint32_t>(S);
+    a.bad = c.take<uint32_t>(S);
+    a.cbeg = c.take<uint32_t>(S);
+    a.cend = c.take<uint32_t>(S);
+    a.ofend = c.take<uint32_t>(S);
+    if constexpr (A::kRelay) {
+        a.pcnt = c.take<uint64_t>(S + 1);
+        a.pbytes = c.take<uint64_t>(S + 1);
+        a.rbytes = c.take<uint64_t>(S);
+        a.agg_h = c.take<uint64_t>(ns);
+        a.agg_pc = c.take<uint64_t>(ns);
+        a.agg_pb = c.take<uint64_t>(ns);
+        a.skey[0] = c.take<uint32_t>(S);
+        a.skey[1] = c.take<uint32_t>(S);
+        a.sidx[0] = c.take<uint32_t>(S);
+        a.sidx[1] = c.take<uint32_t>(S);
+        a.hist = c.take<uint32_t>(ns * kBlock);
+        a.rcnt = c.take<uint32_t>(S);
+        a.written = c.take<uint32_t>(1);
+    }
+    if constexpr (A::kAnswer) {
+        a.agg_rep = c.take<uint64_t>(nb);
+        a.rbeg = c.take<uint64_t>(S);
+        a.rend = c.take<uint64_t>(S);
+    }
+}
 
 template <class A>
 int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     constexpr bool relay = A::kRelay;
     static_assert(sizeof(uvhttp_ws_echo_conn_t) == 32 && sizeof(uvhttp_ws_echo_summary_t) == 32, "ABI");
     static_assert(sizeof(uvhttp_ws_answer_conn_t) == 32 && sizeof(uvhttp_ws_answer_summary_t) == 32, "ABI");
-    const uint64_t F = a.max_frames, S = a.n_streams, E = a.max_echoes;
-    const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
-    const uint32_t grid_s = (uint32_t)((S + kBlock - 1) / kBlock);
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.max_frames + kBlock - 1) / kBlock);
+    const uint32_t grid_s = (uint32_t)(((uint64_t)a.n_streams + kBlock - 1) / kBlock);
     const uint64_t nb = blocks ? blocks : 1, ns = grid_s ? grid_s : 1;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes);
-        return at;
-    };
-    const size_t o_elem = take(F * 8), o_dsum = take(F * 8), o_view = take(F * 8);
-    const size_t o_amark = take(nb * 8), o_ad = take(nb * 8), o_apost = take(nb * 8);
-    const size_t o_acnt = take(nb * 8), o_abytes = take(nb * 8), o_acn = take(ns * 8), o_aco = take(ns * 8);
-    const size_t o_bbeg = take(S * 8), o_bend = take(S * 8), o_olen = take(S * 8), o_omark = take(S * 8);
-    const size_t o_rec = take(E * sizeof(EcRec)), o_orec = take(S * sizeof(EcRec));
-    const size_t o_marks = take(F * 4);
     const uint64_t tiles_out = (a.out_cap + kTile - 1) / kTile;
     const uint64_t tiles_open = a.open ? (a.open_cap + kTile - 1) / kTile : 0;
-    const size_t o_tmap = take((tiles_out + 1) * 4), o_omap = take((tiles_open + 1) * 4);
-    const size_t o_cstate = take(S * 4), o_close = take(S * 4), o_bad = take(S * 4);
-    const size_t o_cbeg = take(S * 4), o_cend = take(S * 4), o_ofend = take(S * 4);
-    // the relay's (nothing for the echo)
-    const uint64_t R = relay ? 1 : 0;
-    const size_t o_pcnt = take(R * (S + 1) * 8), o_pbytes = take(R * (S + 1) * 8), o_rbytes = take(R * S * 8);
-    const size_t o_aggh = take(R * ns * 8), o_aggpc = take(R * ns * 8), o_aggpb = take(R * ns * 8);
-    const size_t o_skey0 = take(R * S * 4), o_skey1 = take(R * S * 4), o_sidx0 = take(R * S * 4), o_sidx1 = take(R * S * 4);
-    const size_t o_hist = take(R * ns * kBlock * 4), o_rcnt = take(R * S * 4), o_written = take(R * 4);
-    // the answers' (nothing for the others)
-    const uint64_t N = A::kAnswer ? 1 : 0;
-    const size_t o_arep = take(N * nb * 8), o_rbeg = take(N * S * 8), o_rend = take(N * S * 8);
-    // radix passes: the bits of the largest key, n_rooms
-    uint32_t passes = 0;
-    if constexpr (relay)
-        for (uint64_t top = a.n_rooms; top; top >>= 8) ++passes;
+    Carver count{nullptr};
+    ec_carve(count, a, nb, ns, tiles_out, tiles_open);
 
     hipStream_t s = (hipStream_t)stream;
     const int prev = uvws_call_enter(e, s);
-    char* mem = static_cast<char*>(uvws_echo_scratch(e, off ? off : 256, s));
+    char* mem = static_cast<char*>(uvws_echo_scratch(e, count.bytes(), s));
     if (!mem) {
         (void)uvws_call_leave(e, prev, what);
         return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "echo_messages scratch (a captured call must not grow it)");
     }
-    a.elem = reinterpret_cast<uint64_t*>(mem + o_elem);
-    a.dsum = reinterpret_cast<uint64_t*>(mem + o_dsum);
-    a.view = reinterpret_cast<uint64_t*>(mem + o_view);
-    a.agg_mark = reinterpret_cast<uint64_t*>(mem + o_amark);
-    a.agg_d = reinterpret_cast<uint64_t*>(mem + o_ad);
-    a.agg_post = reinterpret_cast<uint64_t*>(mem + o_apost);
-    a.agg_cnt = reinterpret_cast<uint64_t*>(mem + o_acnt);
-    a.agg_bytes = reinterpret_cast<uint64_t*>(mem + o_abytes);
-    a.agg_cn = reinterpret_cast<uint64_t*>(mem + o_acn);
-    a.agg_co = reinterpret_cast<uint64_t*>(mem + o_aco);
-    a.bbeg = reinterpret_cast<uint64_t*>(mem + o_bbeg);
-    a.bend = reinterpret_cast<uint64_t*>(mem + o_bend);
-    a.olen = reinterpret_cast<uint64_t*>(mem + o_olen);
-    a.omark = reinterpret_cast<uint64_t*>(mem + o_omark);
-    a.rec = reinterpret_cast<EcRec*>(mem + o_rec);
-    a.orec = reinterpret_cast<EcRec*>(mem + o_orec);
-    a.marks = reinterpret_cast<uint32_t*>(mem + o_marks);
-    a.tmap = reinterpret_cast<uint32_t*>(mem + o_tmap);
-    a.omap = reinterpret_cast<uint32_t*>(mem + o_omap);
-    a.cstate = reinterpret_cast<uint32_t*>(mem + o_cstate);
-    a.first_close = reinterpret_cast<uint32_t*>(mem + o_close);
-    a.bad = reinterpret_cast<uint32_t*>(mem + o_bad);
-    a.cbeg = reinterpret_cast<uint32_t*>(mem + o_cbeg);
-    a.cend = reinterpret_cast<uint32_t*>(mem + o_cend);
-    a.ofend = reinterpret_cast<uint32_t*>(mem + o_ofend);
+    Carver carve{mem};
+    ec_carve(carve, a, nb, ns, tiles_out, tiles_open);
+    // radix passes: the bits of the largest key, n_rooms
+    uint32_t passes = 0;
     if constexpr (relay) {
-        a.pcnt = reinterpret_cast<uint64_t*>(mem + o_pcnt);
-        a.pbytes = reinterpret_cast<uint64_t*>(mem + o_pbytes);
-        a.rbytes = reinterpret_cast<uint64_t*>(mem + o_rbytes);
-        a.agg_h = reinterpret_cast<uint64_t*>(mem + o_aggh);
-        a.agg_pc = reinterpret_cast<uint64_t*>(mem + o_aggpc);
-        a.agg_pb = reinterpret_cast<uint64_t*>(mem + o_aggpb);
-        a.skey[0] = reinterpret_cast<uint32_t*>(mem + o_skey0);
-        a.skey[1] = reinterpret_cast<uint32_t*>(mem + o_skey1);
-        a.sidx[0] = reinterpret_cast<uint32_t*>(mem + o_sidx0);
-        a.sidx[1] = reinterpret_cast<uint32_t*>(mem + o_sidx1);
+        for (uint64_t top = a.n_rooms; top; top >>= 8) ++passes;
         a.okey = a.skey[passes & 1];
         a.oidx = a.sidx[passes & 1];
-        a.hist = reinterpret_cast<uint32_t*>(mem + o_hist);
-        a.rcnt = reinterpret_cast<uint32_t*>(mem + o_rcnt);
-        a.written = reinterpret_cast<uint32_t*>(mem + o_written);
     }
-    if constexpr (A::kAnswer) {
-        a.agg_rep = reinterpret_cast<uint64_t*>(mem + o_arep);
-        a.rbeg = reinterpret_cast<uint64_t*>(mem + o_rbeg);
-        a.rend = reinterpret_cast<uint64_t*>(mem + o_rend);
-        a.tot_rep = blocks && grid_s ? a.agg_rep + (blocks - 1) : nullptr;
-    }
+    if constexpr (A::kAnswer) a.tot_rep = blocks && grid_s ? a.agg_rep + (blocks - 1) : nullptr;
     const bool frames = blocks && grid_s;  // else no echo: the totals are 0
     a.tot_cnt = frames ? a.agg_cnt + (blocks - 1) : nullptr;
     a.tot_bytes = frames ? a.agg_bytes + (blocks - 1) : nullptr;
@@ -1337,22 +1242,22 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     hipLaunchKernelGGL((k_echo_init<A>), dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
     if (grid_s) hipLaunchKernelGGL((k_echo_conns<A>), dim3(grid_s), dim3(kBlock), 0, s, a);
     if (frames) {
-        hipLaunchKernelGGL(k_echo_reduce, dim3(blocks), dim3(kBlock), 0, s, base);
-        hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, blocks);
+        hipLaunchKernelGGL((k_mark_reduce<>), dim3(blocks), dim3(kBlock), 0, s, a.marks, a.max_frames, a.agg_mark, (uint64_t)0);
+        hipLaunchKernelGGL((k_scan_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, a.agg_mark, blocks);
         // (the relay classifies as the echo does: the echo's instance)
         if constexpr (A::kAnswer) hipLaunchKernelGGL((k_echo_classify<A>), dim3(blocks), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_echo_classify<EcArgs>), dim3(blocks), dim3(kBlock), 0, s, base);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_d, blocks);
-        hipLaunchKernelGGL((k_echo_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_post, blocks);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_d, a.agg_d, blocks);
+        hipLaunchKernelGGL((k_scan_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_post, a.agg_post, blocks);
         hipLaunchKernelGGL(k_echo_prefix, dim3(blocks), dim3(kBlock), 0, s, base);
         hipLaunchKernelGGL((k_echo_size<A>), dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cnt, blocks);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_bytes, blocks);
-        if constexpr (A::kAnswer) hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_rep, blocks);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cnt, a.agg_cnt, blocks);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_bytes, a.agg_bytes, blocks);
+        if constexpr (A::kAnswer) hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_rep, a.agg_rep, blocks);
     }
     if (grid_s) {
         hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, base, 1);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_co, grid_s);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_co, a.agg_co, grid_s);
     }
     if constexpr (relay) if (grid_s) {
         // every connection's frames and bytes, the order, and each connection's base in it
@@ -1370,7 +1275,7 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
             engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
                 hipLaunchKernelGGL(k_relay_hreduce, dim3(grid), dim3(kBlock), 0, s, a, tb);
             });
-            hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_h, grid_s);
+            hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_h, a.agg_h, grid_s);
             engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
                 hipLaunchKernelGGL(k_relay_hscan, dim3(grid), dim3(kBlock), 0, s, a, tb);
             });
@@ -1381,14 +1286,14 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
         engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
             hipLaunchKernelGGL(k_relay_oreduce, dim3(grid), dim3(kBlock), 0, s, a, tb);
         });
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pc, grid_s);
-        hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pb, grid_s);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pc, a.agg_pc, grid_s);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_pb, a.agg_pb, grid_s);
         engine_grid_chunks(e, grid_s, [&](uint32_t grid, uint64_t tb) {
             hipLaunchKernelGGL(k_relay_obase, dim3(grid), dim3(kBlock), 0, s, a, tb);
         });
     }
     if (frames) hipLaunchKernelGGL((k_echo_offsets<A>), dim3(blocks), dim3(kBlock), 0, s, a);
-    const uint32_t grid_t = (uint32_t)((E + 1 + kBlock - 1) / kBlock);
+    const uint32_t grid_t = (uint32_t)(((uint64_t)a.max_echoes + 1 + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_echo_tail, dim3(grid_t), dim3(kBlock), 0, s, base);
     if constexpr (relay) {
         engine_grid_chunks(e, ((uint64_t)a.n_rooms + kBlock - 1) / kBlock, [&](uint32_t grid, uint64_t tb) {
@@ -1401,7 +1306,7 @@ int ec_run(uvhttp_ws_gpu_engine_t* e, A a, void* stream, const char* what) {
     if (grid_s) {
         if constexpr (!relay) {
             hipLaunchKernelGGL(k_echo_creduce, dim3(grid_s), dim3(kBlock), 0, s, base, 0);
-            hipLaunchKernelGGL((k_echo_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cn, grid_s);
+            hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_cn, a.agg_cn, grid_s);
         }
         hipLaunchKernelGGL((k_echo_finish<A>), dim3(grid_s), dim3(kBlock), 0, s, a);
         engine_grid_chunks(e, tiles_out + tiles_open, [&](uint32_t grid, uint64_t tb) {

@@ -8,8 +8,8 @@
 //   k_fp_init      marks[f] = 0 per descriptor; the summary zeroed
 //   k_fp_conns     one lane per connection: first_close = none, and a head mark (connection + 1)
 //                  at the first considered descriptor of a judged connection
-//   k_fp_reduce    one lane per descriptor: the workgroup's last head mark
-//   k_fp_top       one workgroup: the aggregates' inclusive prefixes
+//   k_mark_reduce  one lane per descriptor: the workgroup's last head mark (ws_scan.h)
+//   k_scan_top     one workgroup: the aggregates' inclusive prefixes (ws_scan.h)
 //   k_fp_classify  one lane per descriptor, 32 bytes read each: its connection from the scan of
 //                  the marks (the last head at or before it); a CLOSE with status OK inside the
 //                  connection's considered range lowers first_close[connection] (atomicMin)
@@ -28,12 +28,9 @@
 
 #include "uvhttp_ws_amd.h"
 #include "ws_engine_int.h"
+#include "ws_scan.h"
 
 namespace {
-
-constexpr int kBlock = 256;  // the scan block: descriptors (or connections) per workgroup
-constexpr int kWaves = kBlock / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 struct FpArgs {
     const uint8_t* wire;
@@ -55,48 +52,13 @@ struct FpArgs {
     uint32_t* first_close;  // [n_streams] the connection's first considered CLOSE, kNone if none
 };
 
-// the later head mark
-__device__ __forceinline__ uint64_t last_of(uint64_t a, uint64_t b) { return b ? b : a; }
-
-// inclusive "last head mark" scan over the workgroup's kBlock lanes; *total = all of them.  Every
-// lane calls it.
-__device__ __forceinline__ uint64_t block_scan_last(uint64_t v, uint64_t* s_wave, uint64_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v = last_of(o, v);
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[w] = v;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) pre = last_of(pre, s_wave[k]);
-        tot = last_of(tot, s_wave[k]);
-    }
-    *total = tot;
-    return last_of(pre, v);
-}
-
-__device__ __forceinline__ bool call_failed(int32_t fs) {
-    return fs == UVHTTP_WS_FRAME_ERR_CAPACITY || fs == UVHTTP_WS_FRAME_ERR_LAYOUT || fs == UVHTTP_WS_FRAME_ERR_DEVICE;
-}
-
-// connection s's considered descriptors [ff, ff + nd), inside [0, max_frames); none when the
-// connection is not judged
-struct FpRange {
-    uint32_t ff, nd;
-};
-
-__device__ __forceinline__ FpRange conn_range(const FpArgs& a, uint32_t s) {
+// connection s's considered descriptors, inside [0, max_frames); none when the connection is not
+// judged: the call failed, or (this call alone) the connection is not enabled
+__device__ __forceinline__ Range conn_range(const FpArgs& a, uint32_t s) {
     const uvhttp_ws_stream_result_t& q = a.results[s];
-    FpRange r = {q.first_frame, q.n_delivered};
+    Range r = {q.first_frame, q.n_delivered};
     if (call_failed(q.first_status) || (a.enable && a.enable[s] == 0)) r.nd = 0;
-    if (r.ff >= a.max_frames) r.nd = 0;
-    else if (r.nd > a.max_frames - r.ff) r.nd = a.max_frames - r.ff;
-    return r;
+    return clamp_range(r, a.max_frames);
 }
 
 __device__ __forceinline__ bool code_valid(uint32_t c) {
@@ -117,38 +79,8 @@ __global__ __launch_bounds__(kBlock) void k_fp_conns(FpArgs a, uint64_t tb) {
     const uint64_t s = (tb + blockIdx.x) * kBlock + threadIdx.x;
     if (s >= a.n_streams) return;
     a.first_close[s] = kNone;
-    const FpRange r = conn_range(a, (uint32_t)s);
+    const Range r = conn_range(a, (uint32_t)s);
     if (r.nd) a.marks[r.ff] = (uint32_t)s + 1;
-}
-
-__global__ __launch_bounds__(kBlock) void k_fp_reduce(FpArgs a, uint64_t tb) {
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t b = tb + blockIdx.x;
-    const uint64_t f = b * kBlock + threadIdx.x;
-    const uint64_t m = f < a.max_frames ? a.marks[f] : 0;
-    uint64_t tot;
-    (void)block_scan_last(m, s_wave, &tot);
-    if (threadIdx.x == 0) a.agg_mark[b] = tot;
-}
-
-// one workgroup: agg[0, n) -> inclusive prefixes.  Every lane folds its own run of entries, the
-// runs' totals are scanned once, and the lane writes its run back with the prefix in front.
-__global__ __launch_bounds__(kBlock) void k_fp_top(uint64_t* agg, uint32_t n) {
-    __shared__ uint64_t s_wave[kWaves];
-    __shared__ uint64_t s_inc[kBlock];
-    const uint32_t per = (n + kBlock - 1) / kBlock;
-    const uint64_t lo = (uint64_t)threadIdx.x * per;
-    const uint64_t hi = lo + per < n ? lo + per : n;
-    uint64_t run = 0;
-    for (uint64_t i = lo; i < hi; ++i) run = last_of(run, agg[i]);
-    uint64_t tot;
-    s_inc[threadIdx.x] = block_scan_last(run, s_wave, &tot);
-    __syncthreads();
-    uint64_t acc = threadIdx.x ? s_inc[threadIdx.x - 1] : 0;  // the runs before this lane's
-    for (uint64_t i = lo; i < hi; ++i) {
-        acc = last_of(acc, agg[i]);
-        agg[i] = acc;
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_fp_classify(FpArgs a, uint64_t tb) {
@@ -156,15 +88,12 @@ __global__ __launch_bounds__(kBlock) void k_fp_classify(FpArgs a, uint64_t tb) {
     const uint64_t b = tb + blockIdx.x;
     const uint64_t f = b * kBlock + threadIdx.x;
     const bool live = f < a.max_frames;
-    const uint64_t m = live ? a.marks[f] : 0;
-    const uint64_t pre = b ? a.agg_mark[b - 1] : 0;
-    uint64_t tot;
-    const uint64_t head = last_of(pre, block_scan_last(m, s_wave, &tot));
+    const uint64_t head = head_mark(a.marks, a.max_frames, a.agg_mark, b, s_wave);
     if (!live || head == 0 || head - 1 >= a.n_streams) return;
     const uvhttp_ws_frame_desc_t& d = a.desc[f];
     if (d.opcode != UVHTTP_WS_OPCODE_CLOSE || d.status != UVHTTP_WS_FRAME_OK) return;
     const uint32_t conn = (uint32_t)(head - 1);
-    const FpRange r = conn_range(a, conn);
+    const Range r = conn_range(a, conn);
     if (f >= r.ff && f - r.ff < r.nd) atomicMin(&a.first_close[conn], (uint32_t)f);
 }
 
@@ -182,10 +111,8 @@ __global__ __launch_bounds__(kBlock) void k_fp_judge(FpArgs a, uint64_t tb) {
         const int32_t fs = r.first_status;
         const bool judged = !call_failed(fs) && !(a.enable && a.enable[s] == 0);
         if (judged) {
-            const uint32_t ff = r.first_frame;
-            uint32_t nd = r.n_delivered;
-            if (ff >= a.max_frames) nd = 0;
-            else if (nd > a.max_frames - ff) nd = a.max_frames - ff;
+            const Range in = clamp_range({r.first_frame, r.n_delivered}, a.max_frames);
+            const uint32_t ff = in.ff, nd = in.nd;
             const uint32_t c = nd ? a.first_close[s] : kNone;  // (no mark, no CLOSE found)
             uint32_t k = kNone;
             if ((a.flags & UVHTTP_WS_FAIL_CHECK_CLOSE) && c != kNone) {
@@ -256,7 +183,11 @@ __global__ __launch_bounds__(kBlock) void k_fp_judge(FpArgs a, uint64_t tb) {
     if (m_any) atomicMin(&a.sum->first_failed, (uint32_t)(s + (uint64_t)(__ffsll((unsigned long long)m_any) - 1)));
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+void fp_carve(Carver& c, FpArgs& a, uint64_t blocks) {
+    a.agg_mark = c.take<uint64_t>(blocks ? blocks : 1);
+    a.marks = c.take<uint32_t>(a.max_frames);
+    a.first_close = c.take<uint32_t>(a.n_streams);
+}
 
 }  // namespace
 
@@ -291,23 +222,20 @@ extern "C" int uvhttp_ws_gpu_fail_points_streams(
     a.verdict_out = d_verdict_out;
     a.fail = d_fail;
     a.sum = d_summary;
-    const uint64_t F = max_frames, S = n_streams;
-    const uint64_t blocks = (F + kBlock - 1) / kBlock, grid_s = (S + kBlock - 1) / kBlock;
-    const size_t o_amark = 0;
-    const size_t o_marks = align_up((blocks ? blocks : 1) * 8);
-    const size_t o_close = o_marks + align_up(F * 4);
-    const size_t bytes = o_close + align_up(S * 4);
+    const uint64_t blocks = ((uint64_t)max_frames + kBlock - 1) / kBlock;
+    const uint64_t grid_s = ((uint64_t)n_streams + kBlock - 1) / kBlock;
+    Carver count{nullptr};
+    fp_carve(count, a, blocks);
 
     hipStream_t s = (hipStream_t)stream;
     const int prev = uvws_call_enter(e, s);
-    char* mem = static_cast<char*>(uvws_fail_scratch(e, bytes, s));
+    char* mem = static_cast<char*>(uvws_fail_scratch(e, count.bytes(), s));
     if (!mem) {
         (void)uvws_call_leave(e, prev, "fail_points_streams launch");
         return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "fail_points scratch (a captured call must not grow it)");
     }
-    a.agg_mark = reinterpret_cast<uint64_t*>(mem + o_amark);
-    a.marks = reinterpret_cast<uint32_t*>(mem + o_marks);
-    a.first_close = reinterpret_cast<uint32_t*>(mem + o_close);
+    Carver carve{mem};
+    fp_carve(carve, a, blocks);
     // (one workgroup at least: it zeroes the summary)
     engine_grid_chunks(e, blocks ? blocks : 1, [&](uint32_t grid, uint64_t tb) {
         hipLaunchKernelGGL(k_fp_init, dim3(grid), dim3(kBlock), 0, s, a, tb);
@@ -317,9 +245,9 @@ extern "C" int uvhttp_ws_gpu_fail_points_streams(
     });
     if (blocks && grid_s) {
         engine_grid_chunks(e, blocks, [&](uint32_t grid, uint64_t tb) {
-            hipLaunchKernelGGL(k_fp_reduce, dim3(grid), dim3(kBlock), 0, s, a, tb);
+            hipLaunchKernelGGL((k_mark_reduce<>), dim3(grid), dim3(kBlock), 0, s, a.marks, a.max_frames, a.agg_mark, tb);
         });
-        hipLaunchKernelGGL(k_fp_top, dim3(1), dim3(kBlock), 0, s, a.agg_mark, (uint32_t)blocks);
+        hipLaunchKernelGGL((k_scan_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, a.agg_mark, (uint32_t)blocks);
         engine_grid_chunks(e, blocks, [&](uint32_t grid, uint64_t tb) {
             hipLaunchKernelGGL(k_fp_classify, dim3(grid), dim3(kBlock), 0, s, a, tb);
         });

@@ -7,8 +7,8 @@
 //   k_rp_init      marks[f] = 0 per descriptor; the summary zeroed
 //   k_rp_conns     one lane per connection: its scratch words, and a head mark (connection + 1)
 //                  at its first delivered descriptor
-//   k_rp_reduce    one lane per descriptor: the workgroup's last head mark
-//   k_rp_top       one workgroup: the aggregates' inclusive prefixes
+//   k_mark_reduce  one lane per descriptor: the workgroup's last head mark (ws_scan.h)
+//   k_scan_top     one workgroup: the aggregates' inclusive prefixes (ws_scan.h)
 //   k_rp_classify  one lane per descriptor, 32 bytes read each: its connection from the scan of
 //                  the marks (the last head at or before it); inside the connection's delivered
 //                  range it writes a word — the connection, first / last frame of the range, and
@@ -18,7 +18,7 @@
 //   k_rp_size      one lane per descriptor, 8 bytes read: a candidate is answered when its
 //                  connection is not bad and it is not after the connection's first CLOSE (or the
 //                  flag says to go on); the workgroup's replies and bytes
-//   k_rp_top       both aggregates (two workgroups)
+//   k_scan_top     both aggregates (two workgroups)
 //   k_rp_emit      one lane per descriptor, 8 bytes read: reply index and byte offset from the
 //                  scan; the running totals before a connection's first frame and after its last
 //                  (its replies and bytes are their difference: no atomics, in place every frame
@@ -27,7 +27,7 @@
 //                  at most three rounds per reply, at whatever alignment the offset has.  So the
 //                  payload is touched only for replies and the emit costs by the reply
 //   k_rp_tail      d_out_off[n_replies .. max_replies] = the total (all 0 on capacity)
-//   k_rp_creduce / k_rp_top / k_rp_finish   one lane per connection: first_reply as the
+//   k_rp_creduce / k_scan_top / k_rp_finish  one lane per connection: first_reply as the
 //                  exclusive sum of the connections' replies, the 16-byte result, the run, the
 //                  summary
 //
@@ -41,12 +41,9 @@
 
 #include "uvhttp_ws_amd.h"
 #include "ws_engine_int.h"
+#include "ws_scan.h"
 
 namespace {
-
-constexpr int kBlock = 256;  // the scan block: descriptors (or connections) per workgroup
-constexpr int kWaves = kBlock / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 // the word per descriptor (elem): bits 0-6 the reply's payload length, then
 constexpr uint64_t kLenMask = 0x7F;
@@ -97,46 +94,9 @@ struct RpArgs {
     uint64_t* bend;
 };
 
-struct LastOp {  // the later head mark
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return b ? b : a; }
-};
-struct AddOp {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-
-// inclusive scan over the workgroup's kBlock lanes; *total = all of them.  Every lane calls it.
-template <typename Op>
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, Op op, uint64_t* s_wave, uint64_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v = op(o, v);
-    }
-    __syncthreads();  // s_wave may still be read from the previous use
-    if (lane == 63) s_wave[w] = v;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        if (k < w) pre = op(pre, s_wave[k]);
-        tot = op(tot, s_wave[k]);
-    }
-    *total = tot;
-    return op(pre, v);
-}
-
-__device__ __forceinline__ bool range_ok(const RpArgs& a, uint64_t off, uint64_t len) {
-    return len <= a.wire_len && off <= a.wire_len - len;
-}
-
-// connection s's considered descriptors [ff, ff + nd), inside [0, max_frames)
-struct RpRange {
-    uint32_t ff, nd;
-};
-
-__device__ __forceinline__ RpRange conn_range(const RpArgs& a, uint32_t s) {
-    RpRange r;
+// connection s's considered descriptors, inside [0, max_frames)
+__device__ __forceinline__ Range conn_range(const RpArgs& a, uint32_t s) {
+    Range r;
     if (!a.results) {
         r.ff = 0;
         r.nd = a.bsum->n_delivered;
@@ -144,13 +104,9 @@ __device__ __forceinline__ RpRange conn_range(const RpArgs& a, uint32_t s) {
         const uvhttp_ws_stream_result_t& q = a.results[s];
         r.ff = q.first_frame;
         r.nd = q.n_delivered;
-        if (q.first_status == UVHTTP_WS_FRAME_ERR_CAPACITY || q.first_status == UVHTTP_WS_FRAME_ERR_LAYOUT ||
-            q.first_status == UVHTTP_WS_FRAME_ERR_DEVICE)
-            r.nd = 0;
+        if (call_failed(q.first_status)) r.nd = 0;
     }
-    if (r.ff >= a.max_frames) r.nd = 0;
-    else if (r.nd > a.max_frames - r.ff) r.nd = a.max_frames - r.ff;
-    return r;
+    return clamp_range(r, a.max_frames);
 }
 
 __device__ __forceinline__ bool conn_enabled(const RpArgs& a, uint32_t s) { return !a.enable || a.enable[s] != 0; }
@@ -176,57 +132,20 @@ __global__ __launch_bounds__(kBlock) void k_rp_conns(RpArgs a) {
     a.cend[s] = 0;
     a.bbeg[s] = 0;
     a.bend[s] = 0;
-    const RpRange r = conn_range(a, (uint32_t)s);
+    const Range r = conn_range(a, (uint32_t)s);
     if (r.nd) a.marks[r.ff] = (uint32_t)s + 1;
-}
-
-__global__ __launch_bounds__(kBlock) void k_rp_reduce(RpArgs a) {
-    __shared__ uint64_t s_wave[kWaves];
-    const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t m = f < a.max_frames ? a.marks[f] : 0;
-    uint64_t tot;
-    (void)block_scan(m, LastOp(), s_wave, &tot);
-    if (threadIdx.x == 0) a.agg_mark[blockIdx.x] = tot;
-}
-
-// one workgroup per column: agg[0, n) -> inclusive prefixes.  Every lane folds its own run of
-// entries, the runs' totals are scanned once, and the lane writes its run back with the prefix
-// in front.
-template <typename Op>
-__global__ __launch_bounds__(kBlock) void k_rp_top(uint64_t* agg0, uint64_t* agg1, uint32_t n) {
-    __shared__ uint64_t s_wave[kWaves];
-    __shared__ uint64_t s_last[kWaves];
-    uint64_t* agg = blockIdx.x ? agg1 : agg0;
-    const uint32_t per = (n + kBlock - 1) / kBlock;
-    const uint64_t lo = (uint64_t)threadIdx.x * per;
-    const uint64_t hi = lo + per < n ? lo + per : n;
-    uint64_t run = 0;
-    for (uint64_t i = lo; i < hi; ++i) run = Op()(run, agg[i]);
-    uint64_t tot;
-    const uint64_t inc = block_scan(run, Op(), s_wave, &tot);
-    const uint64_t left = __shfl_up(inc, 1);  // the runs before this lane's
-    if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t acc = (threadIdx.x & 63) ? left : (threadIdx.x ? s_last[(threadIdx.x >> 6) - 1] : 0);
-    for (uint64_t i = lo; i < hi; ++i) {
-        acc = Op()(acc, agg[i]);
-        agg[i] = acc;
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_rp_classify(RpArgs a) {
     __shared__ uint64_t s_wave[kWaves];
     const uint64_t f = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = f < a.max_frames;
-    const uint64_t m = live ? a.marks[f] : 0;
-    const uint64_t pre = blockIdx.x ? a.agg_mark[blockIdx.x - 1] : 0;
-    uint64_t tot;
-    const uint64_t head = LastOp()(pre, block_scan(m, LastOp(), s_wave, &tot));
+    const uint64_t head = head_mark(a.marks, a.max_frames, a.agg_mark, blockIdx.x, s_wave);
     if (!live) return;
     uint64_t e = 0;
     if (head != 0 && head - 1 < a.n_streams) {
         const uint32_t conn = (uint32_t)(head - 1);
-        const RpRange r = conn_range(a, conn);
+        const Range r = conn_range(a, conn);
         if (f >= r.ff && f - r.ff < r.nd) {
             e = kIn | ((uint64_t)conn << 32) | (f == r.ff ? kFirst : 0) | (f - r.ff == r.nd - 1 ? kLast : 0);
             const uvhttp_ws_frame_desc_t& d = a.desc[f];
@@ -238,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void k_rp_classify(RpArgs a) {
                     uint64_t len = d.payload_len;
                     if (op == UVHTTP_WS_OPCODE_CLOSE && len < 2) len = 0;
                     if (len > 125) len = 125;  // a delivered control frame has at most 125 bytes
-                    if (len != 0 && !range_ok(a, d.payload_off, len)) a.bad[conn] = 1;
+                    if (len != 0 && !range_ok(a.wire_len, d.payload_off, len)) a.bad[conn] = 1;
                     else e |= kCand | (op == UVHTTP_WS_OPCODE_CLOSE ? kClose : 0) | (srv ? 0 : kMasked) | len;
                 }
             }
@@ -266,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void k_rp_size(RpArgs a) {
     }
     // replies << 32 | bytes: a workgroup holds at most 256 replies of at most 131 bytes
     uint64_t tot;
-    (void)block_scan(((e & kAns) ? 1ull << 32 : 0ull) | reply_bytes(e), AddOp(), s_wave, &tot);
+    (void)block_scan(((e & kAns) ? 1ull << 32 : 0ull) | reply_bytes(e), AddOp(), 0, s_wave, &tot);
     if (threadIdx.x == 0) {
         a.agg_cnt[blockIdx.x] = tot >> 32;
         a.agg_bytes[blockIdx.x] = tot & 0xFFFFFFFFull;
@@ -281,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_rp_emit(RpArgs a) {
     const uint32_t mine = reply_bytes(e);
     const bool ans = (e & kAns) != 0;
     uint64_t tot;
-    const uint64_t inc = block_scan((ans ? 1ull << 32 : 0ull) | mine, AddOp(), s_wave, &tot);
+    const uint64_t inc = block_scan((ans ? 1ull << 32 : 0ull) | mine, AddOp(), 0, s_wave, &tot);
     const uint64_t cnt = (blockIdx.x ? a.agg_cnt[blockIdx.x - 1] : 0) + (inc >> 32);       // inclusive
     const uint64_t bytes = (blockIdx.x ? a.agg_bytes[blockIdx.x - 1] : 0) + (inc & 0xFFFFFFFFull);
     if (e & kIn) {
@@ -339,7 +258,7 @@ __global__ __launch_bounds__(kBlock) void k_rp_creduce(RpArgs a) {
     const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const uint64_t n = s < a.n_streams ? a.cend[s] - a.cbeg[s] : 0;
     uint64_t tot;
-    (void)block_scan(n, AddOp(), s_wave, &tot);
+    (void)block_scan(n, AddOp(), 0, s_wave, &tot);
     if (threadIdx.x == 0) a.agg_conn[blockIdx.x] = tot;
 }
 
@@ -349,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void k_rp_finish(RpArgs a) {
     const bool live = s < a.n_streams;
     const uint32_t n = live ? a.cend[s] - a.cbeg[s] : 0;
     uint64_t tot;
-    const uint64_t inc = (blockIdx.x ? a.agg_conn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), s_wave, &tot);
+    const uint64_t inc = (blockIdx.x ? a.agg_conn[blockIdx.x - 1] : 0) + block_scan(n, AddOp(), 0, s_wave, &tot);
     const uint64_t tn = a.tot_cnt ? *a.tot_cnt : 0, tb = a.tot_bytes ? *a.tot_bytes : 0;
     const bool fits = tn <= a.max_replies && tb <= a.out_cap;
     bool closed = false;
@@ -383,47 +302,39 @@ __global__ __launch_bounds__(kBlock) void k_rp_finish(RpArgs a) {
     }
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
+void rp_carve(Carver& c, RpArgs& a, uint64_t nb, uint64_t ns) {
+    const uint64_t F = a.max_frames, S = a.n_streams;
+    a.elem = c.take<uint64_t>(F);
+    a.agg_mark = c.take<uint64_t>(nb);
+    a.agg_cnt = c.take<uint64_t>(nb);
+    a.agg_bytes = c.take<uint64_t>(nb);
+    a.agg_conn = c.take<uint64_t>(ns);
+    a.bbeg = c.take<uint64_t>(S);
+    a.bend = c.take<uint64_t>(S);
+    a.marks = c.take<uint32_t>(F);
+    a.first_close = c.take<uint32_t>(S);
+    a.bad = c.take<uint32_t>(S);
+    a.cbeg = c.take<uint32_t>(S);
+    a.cend = c.take<uint32_t>(S);
+}
 
 int rp_run(uvhttp_ws_gpu_engine_t* e, RpArgs a, void* stream, const char* what) {
     static_assert(sizeof(uvhttp_ws_reply_conn_t) == 16 && sizeof(uvhttp_ws_reply_summary_t) == 32, "ABI");
-    const uint64_t F = a.max_frames, S = a.n_streams;
-    const uint32_t blocks = (uint32_t)((F + kBlock - 1) / kBlock);
-    const uint32_t grid_s = (uint32_t)((S + kBlock - 1) / kBlock);
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.max_frames + kBlock - 1) / kBlock);
+    const uint32_t grid_s = (uint32_t)(((uint64_t)a.n_streams + kBlock - 1) / kBlock);
     const uint64_t nb = blocks ? blocks : 1, ns = grid_s ? grid_s : 1;
-    size_t off = 0;
-    const size_t o_elem = off;   off = align_up(off + F * 8);
-    const size_t o_amark = off;  off = align_up(off + nb * 8);
-    const size_t o_acnt = off;   off = align_up(off + nb * 8);
-    const size_t o_abytes = off; off = align_up(off + nb * 8);
-    const size_t o_aconn = off;  off = align_up(off + ns * 8);
-    const size_t o_bbeg = off;   off = align_up(off + S * 8);
-    const size_t o_bend = off;   off = align_up(off + S * 8);
-    const size_t o_marks = off;  off = align_up(off + F * 4);
-    const size_t o_close = off;  off = align_up(off + S * 4);
-    const size_t o_bad = off;    off = align_up(off + S * 4);
-    const size_t o_cbeg = off;   off = align_up(off + S * 4);
-    const size_t o_cend = off;   off = align_up(off + S * 4);
+    Carver count{nullptr};
+    rp_carve(count, a, nb, ns);
 
     hipStream_t s = (hipStream_t)stream;
     const int prev = uvws_call_enter(e, s);
-    char* mem = static_cast<char*>(uvws_replies_scratch(e, off ? off : 256, s));
+    char* mem = static_cast<char*>(uvws_replies_scratch(e, count.bytes(), s));
     if (!mem) {
         (void)uvws_call_leave(e, prev, what);
         return uvws_set_err(e, UVHTTP_WS_GPU_ENOMEM, "control_replies scratch (a captured call must not grow it)");
     }
-    a.elem = reinterpret_cast<uint64_t*>(mem + o_elem);
-    a.agg_mark = reinterpret_cast<uint64_t*>(mem + o_amark);
-    a.agg_cnt = reinterpret_cast<uint64_t*>(mem + o_acnt);
-    a.agg_bytes = reinterpret_cast<uint64_t*>(mem + o_abytes);
-    a.agg_conn = reinterpret_cast<uint64_t*>(mem + o_aconn);
-    a.bbeg = reinterpret_cast<uint64_t*>(mem + o_bbeg);
-    a.bend = reinterpret_cast<uint64_t*>(mem + o_bend);
-    a.marks = reinterpret_cast<uint32_t*>(mem + o_marks);
-    a.first_close = reinterpret_cast<uint32_t*>(mem + o_close);
-    a.bad = reinterpret_cast<uint32_t*>(mem + o_bad);
-    a.cbeg = reinterpret_cast<uint32_t*>(mem + o_cbeg);
-    a.cend = reinterpret_cast<uint32_t*>(mem + o_cend);
+    Carver carve{mem};
+    rp_carve(carve, a, nb, ns);
     const bool frames = blocks && grid_s;  // else no reply: the totals are 0
     a.tot_cnt = frames ? a.agg_cnt + (blocks - 1) : nullptr;
     a.tot_bytes = frames ? a.agg_bytes + (blocks - 1) : nullptr;
@@ -431,18 +342,18 @@ int rp_run(uvhttp_ws_gpu_engine_t* e, RpArgs a, void* stream, const char* what) 
     hipLaunchKernelGGL(k_rp_init, dim3(blocks ? blocks : 1), dim3(kBlock), 0, s, a);
     if (grid_s) hipLaunchKernelGGL(k_rp_conns, dim3(grid_s), dim3(kBlock), 0, s, a);
     if (frames) {
-        hipLaunchKernelGGL(k_rp_reduce, dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_rp_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, a.agg_mark, blocks);
+        hipLaunchKernelGGL((k_mark_reduce<>), dim3(blocks), dim3(kBlock), 0, s, a.marks, a.max_frames, a.agg_mark, (uint64_t)0);
+        hipLaunchKernelGGL((k_scan_top<LastOp>), dim3(1), dim3(kBlock), 0, s, a.agg_mark, a.agg_mark, blocks);
         hipLaunchKernelGGL(k_rp_classify, dim3(blocks), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL(k_rp_size, dim3(blocks), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_rp_top<AddOp>), dim3(2), dim3(kBlock), 0, s, a.agg_cnt, a.agg_bytes, blocks);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(2), dim3(kBlock), 0, s, a.agg_cnt, a.agg_bytes, blocks);
         hipLaunchKernelGGL(k_rp_emit, dim3(blocks), dim3(kBlock), 0, s, a);
     }
     const uint32_t grid_t = (uint32_t)(((uint64_t)a.max_replies + 1 + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_rp_tail, dim3(grid_t), dim3(kBlock), 0, s, a);
     if (grid_s) {
         hipLaunchKernelGGL(k_rp_creduce, dim3(grid_s), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL((k_rp_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_conn, a.agg_conn, grid_s);
+        hipLaunchKernelGGL((k_scan_top<AddOp>), dim3(1), dim3(kBlock), 0, s, a.agg_conn, a.agg_conn, grid_s);
         hipLaunchKernelGGL(k_rp_finish, dim3(grid_s), dim3(kBlock), 0, s, a);
     }
     return uvws_call_leave(e, prev, what);
