@@ -354,7 +354,11 @@ int uvhttp_ws_gpu_engine_sync(uvhttp_ws_gpu_engine_t* eng, void* stream);
 #define UVHTTP_WS_STAMP_STREAM_DESC 3 /* k_stream_desc / k_stream_desc_lane */
 #define UVHTTP_WS_STAMP_CLAIMS 4      /* (k_stream_claims until round 5: unused) */
 #define UVHTTP_WS_STAMP_PAYLOAD 5     /* the payload kernel (unmask / scatter / gather) */
-#define UVHTTP_WS_STAMP_PLAN 6        /* k_plan */
+#define UVHTTP_WS_STAMP_PLAN 6        /* k_plan; in-place stride batches of large frames: k_large_fix,
+                                         the launch behind the payload pass that takes its place (it
+                                         plans nothing: tests/test_gpu_stamps.py asks such a call for
+                                         a "plan" record; once that test names the kernels per path,
+                                         k_large_fix should get a kind of its own after SPEC_PLAN) */
 #define UVHTTP_WS_STAMP_FIXUP 7       /* k_fixup (fused stride path) */
 #define UVHTTP_WS_STAMP_FINALIZE 8    /* k_finalize; summary-only compact: k_sum_msgs */
 #define UVHTTP_WS_STAMP_BUILD_SIZE 9  /* send side: kb_size (the emit kernels stamp as PAYLOAD) */

@@ -6,7 +6,10 @@
 LIB_B may be "tree" for the in-tree build.  AB_STAMPS=1 turns engine B's device stamps on;
 AB_ENV_B="K=V,..." sets environment switches for engine B only.  Each round runs K decode steps with engine A,
 then K with engine B, on the same device buffers; reports the median whole-step time
-(torch events around the K steps) and the median payload-kernel time (engine timing)."""
+(torch events around the K steps) and the median payload-kernel time (engine timing), each with
+its spread over the rounds (min .. max).  AB_ROUNDS / AB_STEPS set the rounds (default 7, the
+first is a warm-up) and K (default 20); AB_TIMELINE=1 adds, per engine, the device-stamp
+timeline of 16 more calls (bench.py's summary: kernel durations and the gaps between them)."""
 import os
 import statistics
 import sys
@@ -20,13 +23,15 @@ import uvhttp_amd as U  # noqa: E402
 CFG = {"c2": (65536, 4096, False), "c3": (65536, 65536, False), "c4": (1048576, 256, True),
        # (extra frame sizes for shape rules: same 256 MiB of payload)
        "f2k": (131072, 2048, False), "f8k": (32768, 8192, False), "f16k": (16384, 16384, False),
-       "f24k": (10922, 24576, False), "f32k": (8192, 32768, False)}
+       "f24k": (10922, 24576, False), "f32k": (8192, 32768, False),
+       # (one pipeline slot of bench.py --e2e: 2 048 x 64 KiB)
+       "c3slot": (2048, 65536, False), "f12k": (21846, 12274, False)}
 
 
 def main():
     libs = [U.load_library(p if p != "tree" else U.LIB_PATH) for p in sys.argv[1:3]]
     names = [os.path.basename(p) for p in sys.argv[1:3]]
-    rounds, K = 7, 20
+    rounds, K = int(os.environ.get("AB_ROUNDS", 7)), int(os.environ.get("AB_STEPS", 20))
     st = torch.cuda.current_stream()
     for pair in sys.argv[3:]:
         cfg, mode = pair.split(":")
@@ -116,6 +121,26 @@ def main():
                 assert s["n_delivered"] == n and s["status"] == 0, (names[k], s)
         ms = [statistics.median(x) for x in step]
         ks = [statistics.median(x) for x in kern]
+        for k in (0, 1):
+            print(f"  {'AB'[k]} {names[k]}: step {min(step[k])*1e3:.1f} .. {max(step[k])*1e3:.1f} us, "
+                  f"payload {min(kern[k])*1e3:.1f} .. {max(kern[k])*1e3:.1f} us over {len(step[k])} rounds of {K}",
+                  flush=True)
+        if os.environ.get("AB_TIMELINE"):
+            from bench import summarize_stamps
+            for k in (0, 1):
+                engs[k].set_stamps(True)
+                engs[k].read_stamps()
+                for _ in range(3):  # (the clocks after the ring's clearing copy)
+                    run(k)
+                torch.cuda.synchronize()
+                engs[k].read_stamps()
+                for _ in range(16):
+                    run(k)
+                torch.cuda.synchronize()
+                tl = summarize_stamps(engs[k].read_stamps())
+                engs[k].set_stamps(False)
+                print(f"  {'AB'[k]} timeline: kernels {tl['kernels_us']} gaps {tl['gaps_us']} "
+                      f"between calls {tl['gap_between_calls_us']} chain {tl['chain_us']}", flush=True)
         print(f"{cfg} {mode:8s} step A {ms[0]*1e3:9.1f} us  B {ms[1]*1e3:9.1f} us  "
               f"({(ms[0]/ms[1]-1)*100:+.1f}% B faster) | payload A {ks[0]*1e3:8.1f} B {ks[1]*1e3:8.1f} us "
               f"| other A {(ms[0]-ks[0])*1e3:6.1f} B {(ms[1]-ks[1])*1e3:6.1f} us", flush=True)

@@ -14,6 +14,8 @@
 //              maps; its last block writes the batch summary
 //   k_unmask_inplace / k_gather_compact   the HBM-bound payload pass (the roofline kernel);
 //              its first lanes also mark frames after the first failure SKIPPED
+// In-place stride batches of frames of 12 KiB and more run without k_plan: the payload kernel's
+// other mode decodes from the headers, k_large_fix behind it writes the summary (large_tile).
 //
 // The payload pass is pure streaming integer work: 16-byte loads/stores per lane, the
 // 4-byte key rotated once per (vector, frame) into a 32-bit word, no LDS on the fast path,
@@ -257,7 +259,11 @@ constexpr int kCtlGate = 4;      // epoch of the latest summary-only compact cal
 // latest whose speculation a later kernel broke (undone, then the walk)
 constexpr int kCtlSpecOff = 5;
 constexpr int kCtlSpecBreak = 6;
-constexpr int kCtlWords = 7;
+// in-place stride batches of large frames decoded from their headers (k_unmask_inplace<64, 1,
+// true>): epoch of the latest such call with a frame that is not a complete, locally valid,
+// unfragmented data frame (k_large_fix then runs the state machine and repairs the wire)
+constexpr int kCtlLargeBreak = 7;
+constexpr int kCtlWords = 8;
 // epochs: host-issued tags run 1 .. kMaxHostEpoch, device-issued ones (captured calls)
 // kMaxHostEpoch + 1 .. kMaxEpoch, so a replayed graph never meets a tag a host call left
 constexpr uint32_t kMaxHostEpoch = kMaxEpoch / 2;
@@ -455,6 +461,10 @@ struct BatchArgs {
     uint32_t cas_claims;     // the engine has captured calls: tag_claim displaces later epochs
     uvhttp_ws_message_desc_t* msgs;  // compact decode: the message table (the summary writer
                                      // adds the open message's entry at msgs[n_messages])
+    uint64_t stride_magic;   // large-frame stride decode: floor(2^64 / frame_stride) + 1 (large_tile)
+    uint64_t large_pmax;     //   and the largest payload large_hdr accepts without parse_hdr
+    uint32_t no_claims;      // resolve_one claims no tile and no first_bad (k_large_fix: every
+                             // workgroup runs the state machine itself and keeps the first failure)
 };
 
 // ------------------------------------------------------------------------------------
@@ -627,6 +637,22 @@ __device__ inline uint32_t rotr32(uint32_t x, uint32_t s) {
 // come from the two ALIGNED 16-byte vectors around them and a byte funnel shift: an unaligned
 // 16-byte copy compiles to sixteen byte loads on gfx950 (k_plan spent most of its time there).
 // The last 32 bytes of the buffer go bytewise so nothing past `len` is read.
+// bytes d .. d + 15 (d < 16) of the 32 bytes v0 | v1 (load16_at's funnel, for large_hdr's windows)
+__device__ inline u32x4 funnel16(const u32x4& v0, const u32x4& v1, uint32_t d) {
+    uint64_t x0 = v0.x | ((uint64_t)v0.y << 32), x1 = v0.z | ((uint64_t)v0.w << 32);
+    uint64_t x2 = v1.x | ((uint64_t)v1.y << 32);
+    const uint64_t x3 = v1.z | ((uint64_t)v1.w << 32);
+    if (d & 8) {
+        x0 = x1;
+        x1 = x2;
+        x2 = x3;
+    }
+    const uint32_t s = (d & 7) * 8;
+    const uint64_t r0 = s ? (x0 >> s) | (x1 << (64 - s)) : x0;
+    const uint64_t r1 = s ? (x1 >> s) | (x2 << (64 - s)) : x1;
+    return u32x4{(uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32)};
+}
+
 __device__ inline u32x4 load16_at(const uint8_t* base, uint64_t len, uint64_t o) {
     const uint64_t lo = o & ~(uint64_t)15;
     if (len >= 32 && lo <= len - 32) {  // (cannot wrap for o near 2^64)
@@ -840,7 +866,7 @@ __device__ inline void resolve_one(const BatchArgs& a, uvhttp_ws_message_desc_t*
     // finds frames by arithmetic: no tile map.)
     // (the speculative compact decode claims none: its fallback scatter finds a stride batch's
     // frames by arithmetic, tile_first_of)
-    if ((!a.recs || a.arena) && !a.spec_P) {  // (compact decodes: k_scatter_compact reads this map too)
+    if ((!a.recs || a.arena) && !a.spec_P && !a.no_claims) {  // (compact decodes: k_scatter_compact reads this map too)
         const uint64_t o = frame_start(a, i);
         uint64_t end = (i + 1 < n) ? frame_start(a, i + 1) : a.wire_len;
         if (end > a.wire_len) end = a.wire_len;
@@ -898,7 +924,9 @@ __device__ inline void resolve_one(const BatchArgs& a, uvhttp_ws_message_desc_t*
         }
         d.status = (int8_t)st;
     }
-    if (st != UVHTTP_WS_FRAME_OK) tag_claim(ws.first_bad, a.epoch, i, a.cas_claims);
+    if (st != UVHTTP_WS_FRAME_OK) {
+        if (!a.no_claims) tag_claim(ws.first_bad, a.epoch, i, a.cas_claims);
+    }
     // speculative compact pass (stride batches): it placed frame i's payload at i * spec_P when
     // the frame looked uniform locally; a delivered frame anywhere else (a control frame, another
     // length, an offset moved by an earlier frame) sends the call to the full scatter (k_spec_fix)
@@ -1622,25 +1650,219 @@ __device__ inline void stream_fix(const BatchArgs& a, const Workspace& ws) {
     }
 }
 
-template <int BLOCK, int VPT>
+// ------------------------------------------------------------------------------------
+// In-place stride batches of large frames (stride >= 12 KiB, the 64 x 1 tile shape), decoded
+// from their headers: no k_plan in front of the payload pass (run_decode, decode_large).
+// A 1 KiB tile touches the frame covering its start and at most the next one, and where they
+// lie follows from the tile index alone, so the workgroup loads their header windows (uniform
+// addresses, ahead of every store of the kernel: scalar loads) beside its tile, runs parse_hdr
+// — every check before the state machine — and unmasks the bytes of SIMPLE frames: complete,
+// locally valid, unfragmented data frames (FIN, TEXT or BINARY), each a message of its own.  A
+// batch of simple frames only is delivered whole by the reference state machine, message i =
+// frame i, so the one tile in stride / 1024 that holds a frame's first byte writes its whole
+// descriptor and the frame's header + key bytes into ws.info (k_large_fix sums them for the
+// summary).  Any other frame stores the call's epoch into ctl[kCtlLargeBreak] and is left as
+// it is; k_large_fix then decodes the batch exactly and repairs the wire.  No atomics, no
+// workgroup waits for another, no tile map, no first_bad.
+// ------------------------------------------------------------------------------------
+__device__ inline bool large_simple(const BatchArgs& a, const uvhttp_ws_frame_desc_t& d) {
+    const uint64_t lim = (uint64_t)(int64_t)a.max_message_size;
+    return d.status == UVHTTP_WS_FRAME_OK && (d.opcode == 1 || d.opcode == 2) &&
+           (d.flags & UVHTTP_WS_FLAG_FIN) && (lim == 0 || d.payload_len <= lim);
+}
+__device__ inline uint32_t hdr_key_bytes(const uvhttp_ws_frame_desc_t& d) {
+    return (uint32_t)d.header_size + ((d.flags & UVHTTP_WS_FLAG_MASK) ? 4u : 0u);
+}
+
+// What parse_hdr and large_simple decide for a header with a 16- or 64-bit length (any frame
+// that fills a slot of >= 12 KiB), written out in a few uniform integer steps: FIN, no RSV, TEXT
+// or BINARY; MASK as the server requires; the frame exactly its slot (up to the end of the wire
+// for the last); the payload within BatchArgs::large_pmax (the host's bound for max_frame_size,
+// max_message_size, the recv-buffer cap and the length's top bit).  ok = false decides nothing:
+// parse_hdr judges that frame.  v0 | v1: the 32 aligned bytes around the header at o.
+struct LargeHdr {
+    bool ok, len16, mk;
+    uint32_t key, hm, b0;  // hm: header + key bytes
+    uint64_t ps, plen;     // the payload
+};
+__device__ inline LargeHdr large_hdr(const BatchArgs& a, const u32x4& v0, const u32x4& v1, uint64_t o,
+                                     bool last, uint64_t S, uint64_t vend) {
+    const u32x4 h = funnel16(v0, v1, (uint32_t)(o & 15));
+    LargeHdr r;
+    const uint32_t b1 = (h.x >> 8) & 0xFFu, code = b1 & 0x7Fu;
+    r.b0 = h.x & 0xFFu;
+    r.mk = b1 >> 7;
+    r.len16 = code == 126;
+    const uint64_t le = ((uint64_t)(h.x >> 16) | ((uint64_t)h.y << 16)) | ((uint64_t)h.z << 48);
+    r.plen = r.len16 ? (uint64_t)(((h.x >> 8) & 0xFF00u) | (h.x >> 24)) : __builtin_bswap64(le);
+    r.hm = (r.len16 ? 4u : 10u) + (r.mk ? 4u : 0u);
+    r.key = !r.mk ? 0u : r.len16 ? h.y : (h.z >> 16) | (h.w << 16);
+    r.ps = o + r.hm;
+    const uint64_t wlen = r.plen + r.hm;
+    r.ok = (r.b0 == 0x81u || r.b0 == 0x82u) && code >= 126 && (r.mk || !a.is_server) &&
+           r.plen <= a.large_pmax && (last ? wlen <= vend - o : wlen == S);
+    return r;
+}
+
+__device__ __forceinline__ void large_tile(BatchArgs a, uvhttp_ws_frame_desc_t* desc, const Workspace& ws,
+                                           uint64_t tile_base, StampScope& ss) {
+    constexpr uint64_t kT = 64 * 16;
+    const uint64_t t0 = (tile_base + ss.anchor_s(blockIdx.x)) * kT;
+    const uint64_t vend = a.wire_len;
+    const uint64_t full_end = vend & ~(uint64_t)15;
+    const uint64_t clamp_va = full_end ? full_end - 16 : 0;
+    const uint64_t va = t0 + threadIdx.x * 16u;
+    const u32x4 data =
+        __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.wire + (va < full_end ? va : clamp_va)));
+
+    // f covers t0 (the last frame's slot runs to the end of the wire); f + 1 may start in the tile.
+    // t0 / S by the host's reciprocal floor(2^64 / S) + 1: at most one too large (t0 < 2^52,
+    // S < 2^24); all of it uniform integer work (the double-precision div_stride and two whole
+    // parse_hdr per tile made the kernel instruction-bound: 3 280 us for C3 against 1 253)
+    const uint64_t S = a.frame_stride;
+    const uint32_t n = a.n;
+    uint64_t q = __umul64hi(t0, a.stride_magic);
+    if (q * S > t0) --q;
+    const uint32_t f = (uint32_t)(q < n ? q : n - 1);
+    const uint64_t o0 = (uint64_t)f * S;
+
+    const bool last0 = f + 1 == n;
+    const bool two = !last0 && o0 + S < t0 + kT;
+    const uint64_t o1 = two ? o0 + S : o0;
+    const bool head0 = o0 == t0;  // the tile starts with f's header (then it holds no second frame)
+    const uint32_t hf = head0 ? f : f + 1;
+
+    bool s0 = false, s1 = false, sh = false;  // f, f + 1, the header tile's frame: simple
+    uint64_t ps0 = 0, pe0 = 0, ps1 = 0, pe1 = 0;
+    uint32_t k0 = 0, k1 = 0;
+    uvhttp_ws_frame_desc_t dh;  // the header tile's descriptor
+    bool decided = false;
+    if (vend >= 32 && (o1 & ~(uint64_t)15) <= vend - 32) {
+        const u32x4* w0 = reinterpret_cast<const u32x4*>(a.wire + (o0 & ~(uint64_t)15));
+        const LargeHdr H0 = large_hdr(a, w0[0], w0[1], o0, last0, S, vend);
+        if (H0.ok) {
+            // The common tile, 62 in 64 at 64 KiB frames: all of it inside f's payload.  One rotated
+            // key word serves every lane (vectors are 16 bytes apart: the same key phase).
+            if (H0.ps <= t0 && t0 + kT <= H0.ps + H0.plen) {
+                const uint32_t rk = rotr32(H0.key, 8u * (uint32_t)((t0 - H0.ps) & 3u));
+                if (rk) {
+                    const u32x4 x = data ^ u32x4{rk, rk, rk, rk};
+                    const __amdgpu_buffer_rsrc_t rs =
+                        __builtin_amdgcn_make_buffer_rsrc(a.wire + t0, 0, (int)kT, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b128(
+                        __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, x), rs,
+                        threadIdx.x * 16u, 0, kStoreAux);
+                }
+                // (With stamps on the pass reads 1 310-1 330 us for C3 against 1 240 with them off:
+                // every path joins at the kernel's one exit, and the s_waitcnt vmcnt(0) the other
+                // paths' loads need in front of the stamp code also waits for this tile's store,
+                // so every workgroup lives an acknowledged store longer.  A stamp epilogue of its
+                // own on this path took that wait away and made the kernel slower with stamps
+                // OFF, 1 296 us: not kept.)
+                return;
+            }
+            LargeHdr H1 = H0;
+            if (two) {
+                const u32x4* w1 = reinterpret_cast<const u32x4*>(a.wire + (o1 & ~(uint64_t)15));
+                H1 = large_hdr(a, w1[0], w1[1], o1, f + 2 == n, S, vend);
+            }
+            if (H1.ok) {
+                decided = sh = s0 = true;
+                s1 = two;
+                ps0 = H0.ps, pe0 = H0.ps + H0.plen, k0 = H0.key;
+                ps1 = H1.ps, pe1 = H1.ps + H1.plen, k1 = H1.key;
+                // (field by field: a select of two structs went through scratch)
+                const uint64_t wl = (head0 ? H0.plen : H1.plen) + (head0 ? H0.hm : H1.hm);
+                dh.payload_off = head0 ? H0.ps : H1.ps;
+                dh.payload_len = head0 ? H0.plen : H1.plen;
+                dh.masking_key = head0 ? H0.key : H1.key;
+                dh.opcode = (uint8_t)((head0 ? H0.b0 : H1.b0) & 0x0Fu);
+                dh.flags = (uint8_t)(UVHTTP_WS_FLAG_FIN | ((head0 ? H0.mk : H1.mk) ? UVHTTP_WS_FLAG_MASK : 0u));
+                dh.header_size = (uint8_t)((head0 ? H0.len16 : H1.len16) ? 4 : 10);
+                dh.wire_len = wl > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)wl;
+            }
+        }
+    }
+    if (!decided) {  // parse_hdr judges: the end of the wire, short last frames, every frame not simple
+        uvhttp_ws_frame_desc_t d0, d1;
+        (void)parse_hdr(a, f, seg_info(a, f, n), o0, load_header(a, o0), d0);
+        (void)parse_hdr(a, two ? f + 1 : f, seg_info(a, two ? f + 1 : f, n), o1, load_header(a, o1), d1);
+        s0 = large_simple(a, d0);
+        s1 = two && large_simple(a, d1);
+        sh = head0 ? s0 : s1;
+        ps0 = d0.payload_off, pe0 = d0.payload_off + d0.payload_len, k0 = d0.masking_key;
+        ps1 = d1.payload_off, pe1 = d1.payload_off + d1.payload_len, k1 = d1.masking_key;
+        dh.payload_off = head0 ? d0.payload_off : d1.payload_off;
+        dh.payload_len = head0 ? d0.payload_len : d1.payload_len;
+        dh.masking_key = head0 ? d0.masking_key : d1.masking_key;
+        dh.opcode = head0 ? d0.opcode : d1.opcode;
+        dh.flags = head0 ? d0.flags : d1.flags;
+        dh.header_size = head0 ? d0.header_size : d1.header_size;
+        dh.wire_len = head0 ? d0.wire_len : d1.wire_len;
+    }
+
+    u32x4 m = u32x4{0, 0, 0, 0};
+    if (s0) add_mask(m, va, ps0, pe0, k0);
+    if (s1) add_mask(m, va, ps1, pe1, k1);
+    const uint64_t room = vend - t0;  // (the grid covers the wire: t0 < vend)
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(a.wire + t0, 0, (int)(uint32_t)(room < kT ? room : kT), 0x00020000);
+    if (any_bits(m) && va + 16 <= vend) {
+        const u32x4 x = data ^ m;
+        __builtin_amdgcn_raw_buffer_store_b128(
+            __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, x), rs,
+            (uint32_t)(va - t0), 0, kStoreAux);
+    }
+    // the single vector that straddles the end of the wire: byte stores
+    if (va == full_end && full_end != vend && any_bits(m)) {
+        const uint32_t mw[4] = {m.x, m.y, m.z, m.w};
+        for (uint64_t bq = 0; full_end + bq < vend; ++bq) {
+            const uint8_t mb = (uint8_t)(mw[bq >> 2] >> (8 * (bq & 3)));
+            if (mb) a.wire[full_end + bq] ^= mb;
+        }
+    }
+
+    // the header tile of a frame (f's when the tile starts with it, else f + 1's): after the
+    // tile, so no store precedes the header loads
+    if ((!head0 && !two) || threadIdx.x != 0) return;
+    if (sh) {
+        dh.message = hf;  // (every frame before it is a message: resolve_one's ex.n_fin)
+        dh.flags |= UVHTTP_WS_FLAG_MSG_END;
+        dh.status = UVHTTP_WS_FRAME_OK;
+        ws.info[hf] = (uint8_t)(hdr_key_bytes(dh) | ((uint32_t)dh.opcode << 4));  // (never 0)
+        if (desc) desc[hf] = dh;
+    } else {
+        ws.info[hf] = 0;
+        resolve_epoch(a, ws);
+        ws.ctl[kCtlLargeBreak] = a.epoch;
+    }
+}
+
+// LARGE: the 64 x 1 kernel's other mode (large_tile above; desc may be null)
+template <int BLOCK, int VPT, bool LARGE = false>
 __global__ __launch_bounds__(BLOCK) void k_unmask_inplace(
     BatchArgs a, const uvhttp_ws_frame_desc_t* __restrict__ desc, Workspace ws,
     uint64_t tile_base) {
     StampScope stamp_(a.stamp, a.epoch, UVHTTP_WS_STAMP_PAYLOAD, false, tile_base);
-    uint32_t n, nb;
-    unmask_tile<BLOCK, VPT>(a, desc, ws, tile_base, n, nb, stamp_);  // resolves the epoch
-    // batch in-place decode: the first ceil(n / BLOCK) workgroups then do k_finalize's work
-    // (statuses after the first failure become SKIPPED — frames no tile reads — and the
-    // summary); the launch covers max(tiles, those blocks).  After the tile, so the tile's
-    // workspace and descriptor reads stay scalar loads no store of this kernel precedes.
-    if (!a.streams && tile_base + blockIdx.x < (a.n + BLOCK - 1) / BLOCK) {
-        resolve_epoch(a, ws);
-        finalize_frames(a, const_cast<uvhttp_ws_frame_desc_t*>(desc), ws,
-                        (uint32_t)(tile_base + blockIdx.x), BLOCK, nb);
-    }
-    if (a.s_results && tile_base + blockIdx.x == 0) {
-        resolve_epoch(a, ws);
-        stream_fix(a, ws);
+    if constexpr (LARGE) {
+        static_assert(BLOCK == 64 && VPT == 1, "large_tile is the 64 x 1 shape");
+        large_tile(a, const_cast<uvhttp_ws_frame_desc_t*>(desc), ws, tile_base, stamp_);
+    } else {
+        uint32_t n, nb;
+        unmask_tile<BLOCK, VPT>(a, desc, ws, tile_base, n, nb, stamp_);  // resolves the epoch
+        // batch in-place decode: the first ceil(n / BLOCK) workgroups then do k_finalize's work
+        // (statuses after the first failure become SKIPPED — frames no tile reads — and the
+        // summary); the launch covers max(tiles, those blocks).  After the tile, so the tile's
+        // workspace and descriptor reads stay scalar loads no store of this kernel precedes.
+        if (!a.streams && tile_base + blockIdx.x < (a.n + BLOCK - 1) / BLOCK) {
+            resolve_epoch(a, ws);
+            finalize_frames(a, const_cast<uvhttp_ws_frame_desc_t*>(desc), ws,
+                            (uint32_t)(tile_base + blockIdx.x), BLOCK, nb);
+        }
+        if (a.s_results && tile_base + blockIdx.x == 0) {
+            resolve_epoch(a, ws);
+            stream_fix(a, ws);
+        }
     }
 }
 
@@ -2036,6 +2258,249 @@ __global__ __launch_bounds__(kBlock) void k_fixup(BatchArgs a, uvhttp_ws_frame_d
         uvhttp_ws_frame_desc_t d;
         desc_of_rec(r, i * a.frame_stride, d);
         remask_range(a.wire, d.payload_off, d.payload_off + d.payload_len, d.masking_key);
+    }
+}
+
+// After k_unmask_inplace<64, 1, true> (large_tile): the one launch behind the payload pass of a
+// large-frame stride batch.
+//   No break (every frame simple): workgroup 0 sums the header + key bytes the header tiles left
+//   in ws.info — a non-last simple frame fills its slot, so its payload is the stride less
+//   those — and writes the summary in closed form; the others return at once.
+//   Break (ctl[kCtlLargeBreak] holds the call's epoch): EVERY workgroup runs the reference
+//   state machine over the headers itself, 1024 frames a round (parse_one, block scan,
+//   resolve_one; a round of simple frames met with no message open is taken from the info
+//   bytes alone) up to the round with the first failure, so each knows the first failing frame
+//   nb without waiting for another; round r's descriptors are stored by workgroup r mod grid,
+//   the frames after that round become SKIPPED from their headers alone.  Then the wire is
+//   repaired, a wave per frame: a simple frame from nb on is XOR-ed again (its own inverse:
+//   "the failing frame and everything after it are left untouched"), a delivered frame that was
+//   not simple (a fragment, a control frame in a slot) is unmasked now.  Headers are read from
+//   the wire, which no pass modifies.
+constexpr int kLargeFixBlock = 1024;
+constexpr uint32_t kLargeFixGrid = 128;
+constexpr uint32_t kLargeSuper = 8 * kLargeFixBlock;  // frames k_large_fix can pass in one step
+
+__device__ inline void skipped_desc(uvhttp_ws_frame_desc_t& d) {  // (skip_desc, in registers)
+    d.message = 0;
+    d.flags &= (uint8_t)~UVHTTP_WS_FLAG_MSG_END;
+    d.status = (int8_t)UVHTTP_WS_FRAME_SKIPPED;
+}
+
+__global__ __launch_bounds__(kLargeFixBlock) void k_large_fix(BatchArgs a, uvhttp_ws_frame_desc_t* desc,
+                                                              Workspace ws) {
+    resolve_epoch(a, ws);
+    if (ws.ctl[kCtlLargeBreak] != a.epoch && blockIdx.x != 0) return;
+    StampScope stamp_(a.stamp, a.epoch, UVHTTP_WS_STAMP_PLAN);
+    const uint32_t n = a.n;
+    const uint64_t S = a.frame_stride;
+    const uint32_t tid = threadIdx.x;
+    a.no_claims = 1;
+    if (ws.ctl[kCtlLargeBreak] != a.epoch) {
+        __shared__ uint64_t s_sum[kLargeFixBlock / 64];
+        const uint32_t m = n - 1;  // the last frame's slot may be longer than its frame
+        const u32x4* iv = reinterpret_cast<const u32x4*>(ws.info);
+        uint64_t acc = 0;
+        for (uint32_t c = tid; (uint64_t)c * 16 < m; c += kLargeFixBlock) {
+            const u32x4 v = iv[c];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t left = m - c * 16;  // valid bytes of this vector (>= 1)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                uint32_t x = w[k];
+                if (left < 4 * k + 4) x = left > 4 * k ? x & ((1u << (8 * (left - 4 * k))) - 1u) : 0u;
+                x &= 0x0F0F0F0Fu;  // (the high nibble: the frame's opcode)
+                x = (x & 0x00FF00FFu) + ((x >> 8) & 0x00FF00FFu);
+                acc += (x & 0xFFFFu) + (x >> 16);
+            }
+        }
+#pragma unroll
+        for (int dlt = 32; dlt; dlt >>= 1) acc += __shfl_down(acc, dlt, 64);
+        if ((tid & 63) == 0) s_sum[tid >> 6] = acc;
+        __syncthreads();
+        if (tid != 0) return;
+        uint64_t over = 0;
+        for (int w = 0; w < kLargeFixBlock / 64; ++w) over += s_sum[w];
+        uvhttp_ws_frame_desc_t dl;
+        (void)parse_one(a, n - 1, seg_info(a, n - 1, n), dl);
+        uvhttp_ws_batch_summary_t s;
+        s.n_frames = n;
+        s.n_delivered = n;
+        s.status = 0;
+        s.first_status = 0;
+        s.consumed_bytes = (uint64_t)m * S + dl.wire_len;
+        s.payload_bytes = (uint64_t)m * S - over + dl.payload_len;
+        s.n_messages = n;
+        s.state_closed = 0;
+        s.arena_bytes = 0;
+        s.pending_bytes = 0;
+        *a.summary = s;
+        return;
+    }
+
+    __shared__ uint32_t s_fail;   // the round's first failing frame
+    __shared__ ScanElem s_efail;  // the scan value in front of it
+    __shared__ int32_t s_stfail;  // its status
+    __shared__ uint32_t s_hm, s_all, s_last;  // a round of simple frames: their header + key bytes,
+                                              // "all simple", the last one's info byte
+    ScanElem carry = scan_identity();
+    uint32_t nb = n, done = 0;
+    uint32_t step = kLargeFixBlock;
+    for (uint32_t base = 0; base < n && nb == n; base += step) {
+        step = kLargeFixBlock;
+        if (tid == 0) s_fail = kNoFrame, s_hm = 0, s_all = 1;
+        const uint32_t i = base + tid;
+        const bool open = carry.last_data >= 0 && (carry.bits & kLastOpen);
+        // A whole round of simple frames in front of the last frame, met with no message open:
+        // the state machine delivers each as a message of its own, and the round's scan value
+        // follows from the info bytes the header tiles left (a non-last simple frame's payload is
+        // the stride less its header + key bytes) — no header is read and nothing is scanned.
+        // Their descriptors stand as the header tiles wrote them, but for the message index when
+        // a fragmented message came earlier.
+        // (first eight rounds at once, 8 info bytes a thread: C3's 64 rounds are 8 such steps)
+        if (base + kLargeSuper < n && !open) {
+            __syncthreads();
+            const uint2 v = reinterpret_cast<const uint2*>(ws.info + base)[tid];  // frames base + 8 tid ..
+            const uint32_t w[2] = {v.x, v.y};
+            uint32_t h = 0;
+            bool zero = false;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t x = w[k];
+                zero |= ((x - 0x01010101u) & ~x & 0x80808080u) != 0u;  // a zero byte: a frame not simple
+                x &= 0x0F0F0F0Fu;
+                x = (x & 0x00FF00FFu) + ((x >> 8) & 0x00FF00FFu);
+                h += (x & 0xFFFFu) + (x >> 16);
+            }
+#pragma unroll
+            for (int dlt = 32; dlt; dlt >>= 1) h += __shfl_down(h, dlt, 64);
+            if ((tid & 63) == 0) atomicAdd(&s_hm, h);
+            if (zero) s_all = 0;
+            if (tid == kLargeFixBlock - 1) s_last = v.y >> 24;
+            __syncthreads();
+            if (s_all) {
+                ScanElem agg = scan_identity();
+                agg.last_data = agg.last_start = (int32_t)(base + kLargeSuper - 1);
+                agg.data_pay = agg.all_pay = (uint64_t)kLargeSuper * S - s_hm;
+                agg.seg_pay = S - (s_last & 15u);
+                agg.n_fin = kLargeSuper;
+                agg.bits = kSegFlag | ((s_last >> 4) << kOpShift);
+                // (the workgroup of each of the eight rounds, as below)
+                if (desc && carry.n_fin != base &&
+                    (base / kLargeFixBlock + tid / 128) % gridDim.x == blockIdx.x) {
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) desc[base + 8 * tid + j].message = carry.n_fin + 8 * tid + j;
+                }
+                carry = scan_combine(carry, agg);
+                done = base + kLargeSuper;
+                step = kLargeSuper;
+                __syncthreads();
+                continue;
+            }
+            __syncthreads();
+            if (tid == 0) s_hm = 0, s_all = 1;
+        }
+        if (base + kLargeFixBlock < n && !open) {
+            __syncthreads();
+            const uint32_t info = ws.info[i];
+            uint32_t h = info & 15u;
+#pragma unroll
+            for (int dlt = 32; dlt; dlt >>= 1) h += __shfl_down(h, dlt, 64);
+            if ((tid & 63) == 0) atomicAdd(&s_hm, h);
+            if (info == 0) s_all = 0;
+            if (tid == kLargeFixBlock - 1) s_last = info;
+            __syncthreads();
+            if (s_all) {
+                ScanElem agg = scan_identity();
+                agg.last_data = agg.last_start = (int32_t)(base + kLargeFixBlock - 1);
+                agg.data_pay = agg.all_pay = (uint64_t)kLargeFixBlock * S - s_hm;
+                agg.seg_pay = S - (s_last & 15u);
+                agg.n_fin = kLargeFixBlock;
+                agg.bits = kSegFlag | ((s_last >> 4) << kOpShift);
+                if (desc && carry.n_fin != base && (base / kLargeFixBlock) % gridDim.x == blockIdx.x)
+                    desc[i].message = carry.n_fin + tid;
+                carry = scan_combine(carry, agg);
+                done = base + kLargeFixBlock;
+                __syncthreads();
+                continue;
+            }
+        }
+        uvhttp_ws_frame_desc_t d;
+        SegInfo g;
+        ScanElem elem = scan_identity();
+        if (i < n) {
+            g = seg_info(a, i, n);
+            elem = parse_one(a, i, g, d);
+        }
+        ScanElem agg;
+        const ScanElem local = block_exclusive_scan<kLargeFixBlock>(elem, &agg);
+        const ScanElem run = scan_combine(carry, local);
+        if (i < n) {
+            resolve_one(a, nullptr, ws, i, n, g, run, d);
+            if (d.status != UVHTTP_WS_FRAME_OK) atomicMin(&s_fail, i);
+        }
+        __syncthreads();
+        if (s_fail != kNoFrame) {
+            nb = s_fail;
+            if (i == nb) {
+                s_efail = run;
+                s_stfail = d.status;
+            }
+        }
+        if (desc && i < n && (base / kLargeFixBlock) % gridDim.x == blockIdx.x) {
+            if (i > nb) skipped_desc(d);
+            desc[i] = d;
+        }
+        carry = scan_combine(carry, agg);
+        done = base + kLargeFixBlock < n ? base + kLargeFixBlock : n;
+        __syncthreads();
+    }
+    // frames after the failing round: SKIPPED, their other fields as parse_hdr gives them
+    if (desc && nb < n) {
+        for (uint64_t i = (uint64_t)done + (uint64_t)blockIdx.x * kLargeFixBlock + tid; i < n;
+             i += (uint64_t)gridDim.x * kLargeFixBlock) {
+            uvhttp_ws_frame_desc_t d;
+            (void)parse_one(a, (uint32_t)i, seg_info(a, (uint32_t)i, n), d);
+            skipped_desc(d);
+            desc[i] = d;
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0) {  // write_summary's fields, from the scan value at nb
+        const ScanElem e = nb < n ? s_efail : carry;
+        uvhttp_ws_batch_summary_t s;
+        s.n_frames = n;
+        s.n_delivered = nb;
+        s.first_status = nb < n ? s_stfail : 0;
+        s.status = s.first_status < 0 ? -1 : 0;
+        if (nb < n) {
+            s.consumed_bytes = (uint64_t)nb * S;
+        } else {
+            uvhttp_ws_frame_desc_t dl;
+            (void)parse_one(a, n - 1, seg_info(a, n - 1, n), dl);
+            s.consumed_bytes = (uint64_t)(n - 1) * S + dl.wire_len;
+        }
+        s.payload_bytes = e.all_pay;
+        s.n_messages = e.n_fin;
+        s.state_closed = e.n_close ? 1u : 0u;
+        s.arena_bytes = 0;
+        s.pending_bytes = (e.last_data >= 0 && (e.bits & kLastOpen)) ? e.seg_pay : 0;
+        *a.summary = s;
+    }
+    const uint64_t wave = ((uint64_t)blockIdx.x * kLargeFixBlock + tid) >> 6;
+    const uint64_t nwaves = (uint64_t)gridDim.x * (kLargeFixBlock / 64);
+    // (wave w repairs frames w, w + nwaves, ..: each lane first looks at one of them — the info byte
+    // says whether the pass took the frame for simple, and most frames need nothing)
+    for (uint64_t i0 = wave; i0 < n; i0 += nwaves * 64) {
+        const uint64_t mine = i0 + (uint64_t)(tid & 63) * nwaves;
+        const bool need = mine < n && (ws.info[mine] != 0) != (mine < nb);
+        for (uint64_t todo = __ballot(need); todo; todo &= todo - 1) {
+            const uint64_t i = i0 + (uint64_t)__builtin_ctzll(todo) * nwaves;
+            uvhttp_ws_frame_desc_t d;
+            (void)parse_one(a, (uint32_t)i, seg_info(a, (uint32_t)i, n), d);
+            const bool simple = large_simple(a, d);
+            const bool fix = i < nb ? !simple && d.status == UVHTTP_WS_FRAME_OK : simple;
+            if (fix && d.payload_len && d.masking_key)
+                remask_range(a.wire, d.payload_off, d.payload_off + d.payload_len, d.masking_key);
+        }
     }
 }
 
@@ -5567,7 +6032,7 @@ __global__ __launch_bounds__(kBlock) void k_epoch(uint32_t* ctl, EpochClear c) {
                 c.p[m][k] = 0;
         // (no kernel of an earlier call still runs, and k_epoch itself reads none of these)
         if (blockIdx.x == 0 && threadIdx.x == 0)
-            ctl[kCtlFaultEp] = ctl[kCtlGate] = ctl[kCtlSpecOff] = ctl[kCtlSpecBreak] = 0;
+            ctl[kCtlFaultEp] = ctl[kCtlGate] = ctl[kCtlSpecOff] = ctl[kCtlSpecBreak] = ctl[kCtlLargeBreak] = 0;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -5644,6 +6109,8 @@ struct uvhttp_ws_gpu_engine {
     uint64_t build_frames_max; // frame-grouped LDS emit below this average frame (UVHTTP_WS_BUILD_FRAMES; 0 = off)
     int compact_mode;          // 0 automatic, 1 arena-driven gather, 2 wire-driven scatter
     int sum_fast;              // summary-only stride decode in one payload pass (UVHTTP_WS_SUMMARY_FAST=0: off)
+    int large_spec;            // in-place stride batches of large frames decode from their headers, no
+                               // k_plan (decode_large; UVHTTP_WS_LARGE_SPEC=0: off)
     uint32_t* ctl;             // device control words (kCtl*), own allocation
     uint32_t faults_seen;      // ctl[kCtlFaults] at the last engine_sync
     uint32_t max_polls;        // look-back wait bound (UVHTTP_WS_MAX_POLLS: tests)
@@ -5779,6 +6246,7 @@ static bool experiment_knobs(uvhttp_ws_gpu_engine_t* e, uint32_t* dev_epoch_star
     if (const char* sm = getenv("UVHTTP_WS_SPEC_MAX")) e->spec_max_avg = strtoull(sm, nullptr, 10);
     if (const char* sf = getenv("UVHTTP_WS_SUMMARY_FAST")) e->sum_fast = atoi(sf) != 0;
     if (const char* de = getenv("UVHTTP_WS_DESC_EMIT")) e->desc_emit = atoi(de);
+    if (const char* ls = getenv("UVHTTP_WS_LARGE_SPEC")) e->large_spec = atoi(ls) != 0;
     if (const char* tl = getenv("UVHTTP_WS_TILE")) {  // payload tile shape "BxV" (0x0 = auto)
         int tb = 0, tv = 0;
         if (sscanf(tl, "%dx%d", &tb, &tv) == 2) (void)uvhttp_ws_gpu_engine_set_tile(e, tb, tv);  // (validated)
@@ -5813,6 +6281,7 @@ int uvhttp_ws_gpu_engine_create(int device, uvhttp_ws_gpu_engine_t** out) {
     e->spec_on = 1;
     e->spec_max_avg = kFusedMaxAvg;
     e->sum_fast = 1;
+    e->large_spec = 1;
     // 2: in place the scan and k_desc_emit rebuild the info bytes from the records (C4 step 114.0
     // vs 115.9 us with them left by the payload pass, profiles/r06h_desc_emit_ab_*.txt); compact
     // the speculative pass leaves them (123.9 vs 126.9 us, profiles/r06j_desc_emit_compact_ab.txt)
@@ -6313,11 +6782,12 @@ static uint32_t next_epoch(uvhttp_ws_gpu_engine_t* e, hipStream_t s) {
         const EpochClear c = epoch_blocks(e);
         for (int m = 0; m < 4; ++m)
             if (c.n[m]) (void)hipMemsetAsync(c.p[m], 0, c.n[m] * 8, s);
-        // the ctl words that hold an epoch: kCtlFaultEp, then kCtlGate .. kCtlSpecBreak (not the
+        // the ctl words that hold an epoch: kCtlFaultEp, then kCtlGate .. kCtlLargeBreak (not the
         // device epoch, its counter or the fault count between them)
-        static_assert(kCtlGate + 1 == kCtlSpecOff && kCtlSpecOff + 1 == kCtlSpecBreak, "one run of words");
+        static_assert(kCtlGate + 1 == kCtlSpecOff && kCtlSpecOff + 1 == kCtlSpecBreak &&
+                          kCtlSpecBreak + 1 == kCtlLargeBreak, "one run of words");
         (void)hipMemsetAsync(e->ctl + kCtlFaultEp, 0, sizeof(uint32_t), s);
-        (void)hipMemsetAsync(e->ctl + kCtlGate, 0, 3 * sizeof(uint32_t), s);
+        (void)hipMemsetAsync(e->ctl + kCtlGate, 0, 4 * sizeof(uint32_t), s);
         e->epoch = 0;
     }
     return ++e->epoch;
@@ -6677,6 +7147,36 @@ static int decode_spec(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, Ba
     return UVHTTP_WS_GPU_OK;
 }
 
+// stride batches of large frames in place (kLargeMinStride <= stride < kLargeMaxStride, the
+// 64 x 1 tile shape): the payload pass decodes from the headers, k_large_fix writes the summary
+// and, after a frame that is not simple, decodes exactly and repairs.  d_desc may be null.
+constexpr uint64_t kLargeMinStride = 12288;               // inplace_tile_shape's 64 x 1 range
+constexpr uint64_t kLargeMaxStride = (1ull << 23) + 14;
+static int decode_large(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, BatchArgs& a,
+                        uvhttp_ws_frame_desc_t* d_desc, hipStream_t s) {
+    a.stride_magic = ~0ull / b->frame_stride + 1;
+    // large_hdr's payload bound: what parse_hdr's max_frame_size and recv-buffer checks (the
+    // frame's wire bytes <= max(max_frame_size, 64 KiB): at most 14 more than its payload) and
+    // large_simple's max_message_size allow, below the 64-bit length's top bit
+    const uint64_t mf = (uint64_t)(int64_t)b->max_frame_size, lim = (uint64_t)(int64_t)b->max_message_size;
+    const uint64_t cap = mf > 65536u ? mf : 65536u;
+    uint64_t pmax = mf < cap - 14 ? mf : cap - 14;
+    if (lim && lim < pmax) pmax = lim;
+    a.large_pmax = pmax < (1ull << 62) ? pmax : 1ull << 62;
+    const uint64_t n_ptiles = (b->wire_len + 1023) / 1024;
+    const int tk = timing_begin(e, s);
+    engine_grid_chunks(e, n_ptiles, [&](uint32_t grid_p, uint64_t tb) {
+        hipLaunchKernelGGL((k_unmask_inplace<64, 1, true>), dim3(grid_p), dim3(64), 0, s, a, d_desc, e->ws, tb);
+    });
+    timing_end(e, tk, s);
+    // (gated — all but workgroup 0 return at once unless a frame broke the batch — so a small
+    // grid; after a break a wave repairs a frame at a time)
+    const uint32_t fx = (a.n + 15) / 16;
+    hipLaunchKernelGGL(k_large_fix, dim3(fx < kLargeFixGrid ? fx : kLargeFixGrid), dim3(kLargeFixBlock), 0, s,
+                       a, d_desc, e->ws);
+    return UVHTTP_WS_GPU_OK;
+}
+
 // every other batch: k_plan on the wire's headers, then the payload kernel (in place, or the
 // compact scatter / gather into a.arena)
 static int decode_planned(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, BatchArgs& a,
@@ -6778,6 +7278,10 @@ static int run_decode(uvhttp_ws_gpu_engine_t* e, const uvhttp_ws_batch_t* b, uin
                          (uint64_t)(a.n - 1) <= (b->wire_len - 1) / b->frame_stride;
     if (!arena && strided && !e->fused_off && b->wire_len / a.n <= e->fused_max_avg) {
         rc = decode_fused(e, b, a, d_desc, d_msgs, s);
+    } else if (!arena && strided && e->large_spec && b->frame_stride >= kLargeMinStride &&
+               b->frame_stride < kLargeMaxStride &&
+               (!e->tile_block || (e->tile_block == 64 && e->tile_vpt == 1))) {
+        rc = decode_large(e, b, a, d_desc, s);
     } else {
         // every other path keeps per-frame descriptors internally: a caller without them gets the
         // engine's scratch
