@@ -296,7 +296,10 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* eng, const uint8_t* src
  *
  * Returns EINVAL for a null pointer with a non-zero count (summary is always required), for
  * max_fragment > 16384, and for more than 2^26 sends, 2^28 frames or 2^28 records; ENODEV
- * for a null engine where there is no device.  n_sends = 0 returns OK with a zeroed summary. */
+ * for a null engine where there is no device.  n_sends = 0 returns OK with a zeroed summary.
+ * The call is the one-part case of uvhttp_tls_gpu_seal_parts and is planned as such: one part of
+ * base 0 and len frames_len whose runs points at &sends[0].first_frame with run_stride = 32
+ * (sizeof(uvhttp_tls_send_t)) expresses it; only the argument checks above are its own. */
 int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* eng, const uint8_t* frames,
                                uint64_t frames_len, const uint64_t* frame_off,
                                uint32_t n_frames_total, const uvhttp_tls_send_t* sends,

@@ -271,6 +271,54 @@ def test_empty_calls_and_arguments(torch, eng):
     torch.cuda.synchronize()
 
 
+def test_no_frames_no_table(torch, eng):
+    """n_frames_total = 0 with frame_off = NULL (and no frames buffer): a send of no frames
+    succeeds with no record, one that names a frame is out of range, a bad key slot is a key
+    error; nothing of out or the record table is written although both have room"""
+    import uvhttp_amd as U
+    rng = random.Random(44)
+    keys = _mixed_keys(rng, 6)
+    sends = _sends([(3, 0, 0, 1), (4, 0, 1, 2), (5, 0, 0, len(keys))])
+    ref = R.seal_frames_ref(b"", np.zeros(1, np.uint64), sends, keys)
+    assert list(ref["results"]["status"]) == [0, R.REC_RANGE, O.REC_KEY]
+    assert not len(ref["records"]) and ref["out"] == b""
+    out_cap, max_records = 64, 4
+    out = torch.full((out_cap + GUARD,), FILL, dtype=torch.uint8, device="cuda")
+    recs = torch.full(((max_records + 1) * 32,), FILL, dtype=torch.uint8, device="cuda")
+    res = torch.full((len(sends) * 48,), FILL, dtype=torch.uint8, device="cuda")
+    summ = torch.full((32,), FILL, dtype=torch.uint8, device="cuda")
+    d_sends, d_keys = _dev(torch, sends), _dev(torch, keys)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = U.lib().uvhttp_tls_gpu_seal_frames(
+        eng.h, None, 0, None, 0, p(d_sends), len(sends), p(d_keys), len(keys), 0, p(recs),
+        max_records, p(res), p(summ), p(out), out_cap,
+        C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert res.cpu().numpy().view(R.TLS_SEND_RESULT_DT).tobytes() == ref["results"].tobytes()
+    assert summ.cpu().numpy().view(R.TLS_SEND_SUMMARY_DT).tobytes() == ref["summary"].tobytes()
+    assert (out == FILL).all() and (recs == FILL).all()
+
+
+def test_cross_one_scan_block_after_growth(torch):
+    """one engine of its own: a call with 3 frames, then one with 257 frames and 257 sends of one
+    frame each: the scratch grows between the two, and the frame table's 258 scan entries end in
+    a second workgroup that is all but empty"""
+    import uvhttp_amd as U
+    rng = random.Random(45)
+    e = U.TlsEngine(0)
+    try:
+        keys = _mixed_keys(rng, 6)
+        frames, off = R.build_frames([rng.randbytes(n) for n in (5, 0, 200)])
+        _run(torch, e, frames, off, _sends([(1, 0, 3, 0), (2, 1, 2, 3)]), keys, 64)
+        n = 256 + 1
+        frames, off = R.build_frames([rng.randbytes(rng.choice([0, 1, 40, 126])) for _ in range(n)])
+        _run(torch, e, frames, off, _sends([(rng.getrandbits(40), i, 1, i % 6) for i in range(n)]),
+             keys, 64)
+    finally:
+        e.close()
+
+
 def test_chain_without_host_sync(torch, eng):
     """build_frames -> seal_frames -> open_records -> ws_streams -> decode_reads on one stream,
     the descriptors between the calls made on the device, no synchronisation before the end:

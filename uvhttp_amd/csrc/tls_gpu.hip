@@ -2229,15 +2229,20 @@ __global__ __launch_bounds__(kBlock) void k_tls_ws_prefix(const uvhttp_tls_resul
     for (uint64_t o = threadIdx.x; o < n; o += kBlock) q[o] = p[o];
 }
 
-// ---- send side: built frames -> record table (uvhttp_tls_gpu_seal_frames) ---------------------
+// ---- send side: frames -> record table (uvhttp_tls_gpu_seal_frames, _seal_parts, ---------------
+// ---- _seal_parts_coalesced) -------------------------------------------------------------------
 //
-// The plan is scans, no lane walks a send's frames: (1) an exclusive scan over the frames of
+// One planner for the three calls.  A part is a frame table of its own plus a per-send run, all
+// inside one frames buffer; seal_frames is one part whose runs lie inside sends[].  The plan is
+// scans, no lane walks a send's frames: (1) per part, an exclusive scan over its frames of
 // (records at max_fragment, bad frames), shared by every send that names a frame (a broadcast
-// scans once); (2) per send, records / bytes / status from differences of that scan; (3) an
-// exclusive scan over the sends: first_record, out_off, the capacity decision, the totals; (4)
-// one lane per record: binary search of the send by first_record, of the frame by the frame
-// scan, then the chunk.  Then k_tls_seal / k_tls_seal_chacha over the table, their count read
-// from n_total[0].
+// scans once): part p's scan lies at fr_rec / fr_bad [fbase[p], fbase[p] + n_frames_p], its
+// workgroups are blocks [bbase[p], bbase[p + 1]) of one launch; (2) per send, status / records /
+// bytes from differences of those scans over its parts' runs (send_count; a count kernel adds
+// only how a send's records follow from its runs); (3) an exclusive scan over the sends:
+// first_record, out_off, the capacity decision, the totals; (4) one lane per record (a fill
+// kernel): binary search of the send by first_record, then the record's place in the send.
+// Then k_tls_seal / k_tls_seal_chacha over the table, their count read from n_total[0].
 
 struct SendWork {         // send pass 1 -> pass 2 / fill
     uint64_t n_rec;
@@ -2246,10 +2251,11 @@ struct SendWork {         // send pass 1 -> pass 2 / fill
     uint32_t over;        // bytes a record adds to its content: header, nonce, type byte, tag
 };
 
-struct SendArgs {
-    const uint64_t* frame_off;
-    uint64_t frames_len;
-    uint32_t n_frames;
+struct PartsArgs {
+    uvhttp_tls_part_t part[UVHTTP_TLS_MAX_PARTS];
+    uint32_t fbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's entries in fr_rec / fr_bad
+    uint32_t bbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's workgroups in the frame launches
+    uint32_t n_parts;
     uint32_t max_fragment;
     const uvhttp_tls_send_t* sends;
     uint32_t n_sends;
@@ -2260,28 +2266,15 @@ struct SendArgs {
     uvhttp_tls_send_result_t* results;
     uvhttp_tls_send_summary_t* summary;
     uint64_t out_cap;
-    uint64_t* fr_rec;     // [n_frames + 1] records of the frames before f
-    uint32_t* fr_bad;     // [n_frames + 1] bad frames before f
-    uint64_t* fblk;       // per 256 frames: [2b] records, [2b+1] bad frames
+    uint64_t* fr_rec;     // [fbase[n_parts]] records of the part's frames before f
+    uint32_t* fr_bad;     // [fbase[n_parts]] bad frames of the part before f
+    uint64_t* fblk;       // per workgroup of the frame launches: [2b] records, [2b+1] bad frames
     SendWork* sw;
     uint64_t* sblk;       // per 256 sends: [3b] records, [3b+1] bytes, [3b+2] failed sends
     uint32_t* s_first;    // [n_sends] first_record
     uint64_t* s_out;      // [n_sends] out_off
     uint32_t* n_total;    // [0] records to seal (0 on capacity failure), [1] capacity failed
 };
-
-// frame i's records and whether it is bad (offsets decrease, or reach past frames)
-__device__ inline void send_frame(const SendArgs& a, uint32_t i, uint64_t* rec, uint64_t* bad) {
-    *rec = 0;
-    *bad = 0;
-    if (i >= a.n_frames) return;
-    const uint64_t b = a.frame_off[i], e = a.frame_off[i + 1];
-    if (b > e || e > a.frames_len) {
-        *bad = 1;
-        return;
-    }
-    *rec = (e - b + a.max_fragment - 1) / a.max_fragment;
-}
 
 // exclusive prefix, in place, of n_blocks rows of W block sums; one workgroup
 template <int W>
@@ -2305,183 +2298,6 @@ __device__ inline void scan_block_sums(uint64_t* blk, uint32_t n_blocks, uint64_
             p[w] += v;
         }
 }
-
-__global__ __launch_bounds__(kBlock) void k_tls_send_frame_count(SendArgs a) {
-    uint64_t rec, bad, tr, tb;
-    send_frame(a, blockIdx.x * kBlock + threadIdx.x, &rec, &bad);
-    (void)block_exclusive_sum<uint64_t>(rec, &tr);
-    (void)block_exclusive_sum<uint64_t>(bad, &tb);
-    if (threadIdx.x == 0) {
-        a.fblk[2 * blockIdx.x] = tr;
-        a.fblk[2 * blockIdx.x + 1] = tb;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_tls_send_frame_scan(SendArgs a, uint32_t n_blocks) {
-    uint64_t t[2];
-    scan_block_sums<2>(a.fblk, n_blocks, t);
-}
-
-__global__ __launch_bounds__(kBlock) void k_tls_send_frame_write(SendArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    uint64_t rec, bad, tr, tb;
-    send_frame(a, i, &rec, &bad);
-    const uint64_t pr = a.fblk[2 * blockIdx.x] + block_exclusive_sum<uint64_t>(rec, &tr);
-    const uint64_t pb = a.fblk[2 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(bad, &tb);
-    if (i <= a.n_frames) {
-        a.fr_rec[i] = pr;
-        a.fr_bad[i] = (uint32_t)pb;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_tls_send_count(SendArgs a) {
-    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-    uint64_t n_rec = 0, bytes = 0, failed = 0;
-    if (s < a.n_sends) {
-        const uvhttp_tls_send_t sd = a.sends[s];
-        const uint64_t last = (uint64_t)sd.first_frame + sd.n_frames;
-        int32_t st = 0;
-        uint32_t over = 0;
-        if (sd.key >= a.n_keys || sd.key > 0xFFFFu || a.sched[sd.key].nr == 0) {
-            st = UVHTTP_TLS_REC_ERR_KEY;
-        } else if (last > a.n_frames || a.fr_bad[last] != a.fr_bad[sd.first_frame]) {
-            st = UVHTTP_TLS_REC_ERR_RANGE;
-        } else {
-            const KeySched* k = a.sched + sd.key;
-            over = 5 + 16 + explicit_len(k->version, k->cipher) +
-                   (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
-            n_rec = a.fr_rec[last] - a.fr_rec[sd.first_frame];
-            // (no bad frame in the range: its offsets do not decrease)
-            const uint64_t plain = sd.n_frames ? a.frame_off[last] - a.frame_off[sd.first_frame] : 0;
-            bytes = plain + n_rec * over;
-        }
-        failed = st ? 1 : 0;
-        a.sw[s] = SendWork{n_rec, bytes, st, over};
-    }
-    uint64_t tn, tb, tf;
-    (void)block_exclusive_sum<uint64_t>(n_rec, &tn);
-    (void)block_exclusive_sum<uint64_t>(bytes, &tb);
-    (void)block_exclusive_sum<uint64_t>(failed, &tf);
-    if (threadIdx.x == 0) {
-        a.sblk[3 * blockIdx.x] = tn;
-        a.sblk[3 * blockIdx.x + 1] = tb;
-        a.sblk[3 * blockIdx.x + 2] = tf;
-    }
-}
-
-// exclusive prefix of the per-block sums; capacity decision; totals
-__global__ __launch_bounds__(kBlock) void k_tls_send_scan(SendArgs a, uint32_t n_blocks) {
-    uint64_t t[3];
-    scan_block_sums<3>(a.sblk, n_blocks, t);
-    if (threadIdx.x == 0) {
-        const bool fail = t[0] > a.max_records || t[1] > a.out_cap;
-        a.n_total[0] = fail ? 0u : (uint32_t)t[0];
-        a.n_total[1] = fail ? 1u : 0u;
-        uvhttp_tls_send_summary_t sm;
-        memset(&sm, 0, sizeof(sm));
-        sm.out_bytes = t[1];
-        sm.n_records = t[0] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t[0];
-        sm.n_failed = fail ? a.n_sends : (uint32_t)t[2];
-        *a.summary = sm;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_tls_send_write(SendArgs a) {
-    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-    const SendWork sw = s < a.n_sends ? a.sw[s] : SendWork{0, 0, 0, 0};
-    uint64_t tn, tb;
-    const uint64_t first = a.sblk[3 * blockIdx.x] + block_exclusive_sum<uint64_t>(sw.n_rec, &tn);
-    const uint64_t off = a.sblk[3 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(sw.bytes, &tb);
-    if (s >= a.n_sends) return;
-    const uvhttp_tls_send_t sd = a.sends[s];
-    uvhttp_tls_send_result_t r;
-    memset(&r, 0, sizeof(r));
-    r.next_seq = sd.seq;
-    r.status = sw.status;
-    if (a.n_total[1]) {  // capacity: no layout, nothing sealed
-        if (!sw.status) r.status = UVHTTP_TLS_REC_ERR_CAPACITY;
-        a.s_first[s] = 0;
-        a.s_out[s] = 0;
-    } else {
-        r.out_off = off;
-        r.out_len = sw.bytes;
-        r.next_seq = sd.seq + sw.n_rec;
-        r.first_record = (uint32_t)first;
-        r.n_records = (uint32_t)sw.n_rec;
-        r.plain_len = sw.bytes - sw.n_rec * sw.over;
-        a.s_first[s] = (uint32_t)first;
-        a.s_out[s] = off;
-    }
-    a.results[s] = r;
-}
-
-// one lane per record: its send (the last one whose first_record <= r), its frame (the last one
-// of the send whose record prefix <= the record's position in the frame scan), its chunk
-__global__ __launch_bounds__(kBlock) void k_tls_send_fill(SendArgs a) {
-    const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
-    for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
-        uint32_t lo = 0, hi = a.n_sends;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (a.s_first[mid] <= r) lo = mid;
-            else hi = mid;
-        }
-        const uint32_t s = lo;
-        const uvhttp_tls_send_t sd = a.sends[s];
-        const uint64_t k = r - a.s_first[s];
-        const uint64_t pos = a.fr_rec[sd.first_frame] + k;
-        lo = sd.first_frame, hi = sd.first_frame + sd.n_frames;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (a.fr_rec[mid] <= pos) lo = mid;
-            else hi = mid;
-        }
-        const uint64_t fb = a.frame_off[lo], fe = a.frame_off[lo + 1];
-        const uint64_t cut = (pos - a.fr_rec[lo]) * a.max_fragment;  // content bytes before, in the frame
-        const uint64_t left = fe - fb - cut;
-        uvhttp_tls_seal_t o;
-        o.src_off = fb + cut;
-        o.out_off = a.s_out[s] + (fb - a.frame_off[sd.first_frame]) + cut + k * a.sw[s].over;
-        o.seq = sd.seq + k;
-        o.plain_len = left < a.max_fragment ? (uint32_t)left : a.max_fragment;
-        o.key = (uint16_t)sd.key;
-        o.type = sd.type;
-        o.reserved = 0;
-        a.records[r] = o;
-    }
-}
-
-// ---- send side, several parts per send (uvhttp_tls_gpu_seal_parts) ----------------------------
-//
-// A part is a frame table of its own plus a per-send run, all inside one frames buffer.  The plan
-// is the one above with the frame scan done per part: part p's scan lies at fr_rec / fr_bad
-// [fbase[p], fbase[p] + n_frames_p], its workgroups are blocks [bbase[p], bbase[p + 1]) of one
-// launch.  A send's records, bytes and status are sums over its parts' runs; the scan over the
-// sends and its results are k_tls_send_scan / k_tls_send_write as they stand (they read only
-// sends[].seq, sw, sblk and n_total).  The fill finds a record's send, then walks the at most 8
-// parts by their record counts, then searches the frame in that part's scan.
-
-struct PartsArgs {
-    uvhttp_tls_part_t part[UVHTTP_TLS_MAX_PARTS];
-    uint32_t fbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's entries in fr_rec / fr_bad
-    uint32_t bbase[UVHTTP_TLS_MAX_PARTS + 1];  // part p's workgroups in the frame launches
-    uint32_t n_parts;
-    uint32_t max_fragment;
-    const uvhttp_tls_send_t* sends;
-    uint32_t n_sends;
-    uint32_t n_keys;
-    const KeySched* sched;
-    uvhttp_tls_seal_t* records;
-    uint32_t max_records;
-    uint64_t* fr_rec;
-    uint32_t* fr_bad;
-    uint64_t* fblk;       // per workgroup of the frame launches: [2b] records, [2b+1] bad frames
-    SendWork* sw;
-    uint64_t* sblk;
-    const uint32_t* s_first;
-    const uint64_t* s_out;
-    const uint32_t* n_total;
-};
 
 // the part a workgroup of the frame launches works on
 __device__ inline uint32_t parts_of_block(const PartsArgs& a, uint32_t b) {
@@ -2543,7 +2359,13 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_frame_write(PartsArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_tls_parts_count(PartsArgs a) {
+// Pass (2), all of it but how a send's records follow from its runs.  One lane per send: the key
+// check; then its parts' runs in order, each with the range check (a run past its table, or over a
+// bad frame), each good one handed to run(s, p, first, last, plain) with the send's content bytes
+// up to and including it; then recs(s, plain) gives the records of a send without an error, and
+// with them its record overhead and its bytes in out.  sw[s] and the workgroup's three sums.
+template <class Run, class Recs>
+__device__ inline void send_count(const PartsArgs& a, Run run, Recs recs) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     uint64_t n_rec = 0, bytes = 0, failed = 0;
     if (s < a.n_sends) {
@@ -2564,16 +2386,15 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_count(PartsArgs a) {
                     st = UVHTTP_TLS_REC_ERR_RANGE;
                     break;
                 }
-                n_rec += a.fr_rec[fb + last] - a.fr_rec[fb + first];
-                // (no bad frame in the run: its offsets do not decrease)
+                // (no bad frame in the run: its offsets do not decrease and end within q.len)
                 if (n) plain += q.frame_off[last] - q.frame_off[first];
+                run(s, p, first, (uint32_t)last, plain);
             }
-            if (st) {
-                n_rec = 0;
-            } else {
+            if (!st) {
                 const KeySched* k = a.sched + sd.key;
                 over = 5 + 16 + explicit_len(k->version, k->cipher) +
                        (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
+                n_rec = recs(s, plain);
                 bytes = plain + n_rec * over;
             }
         }
@@ -2591,19 +2412,82 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_count(PartsArgs a) {
     }
 }
 
-// one lane per record: its send (the last one whose first_record <= r), its part (the first one
-// whose records, added to those of the parts before it, pass the record's place in the send), its
-// frame (the last one of the part's run whose record prefix <= the place in the part's scan)
+// every frame is cut on its own: a send's records are those of its runs, from the parts' scans
+__global__ __launch_bounds__(kBlock) void k_tls_parts_count(PartsArgs a) {
+    uint64_t n_rec = 0;
+    send_count(
+        a,
+        [&](uint32_t, uint32_t p, uint32_t first, uint32_t last, uint64_t) {
+            const uint64_t* fr = a.fr_rec + a.fbase[p];
+            n_rec += fr[last] - fr[first];
+        },
+        [&](uint32_t, uint64_t) { return n_rec; });
+}
+
+// pass (3): exclusive prefix of the per-block sums; capacity decision; totals
+__global__ __launch_bounds__(kBlock) void k_tls_send_scan(PartsArgs a, uint32_t n_blocks) {
+    uint64_t t[3];
+    scan_block_sums<3>(a.sblk, n_blocks, t);
+    if (threadIdx.x == 0) {
+        const bool fail = t[0] > a.max_records || t[1] > a.out_cap;
+        a.n_total[0] = fail ? 0u : (uint32_t)t[0];
+        a.n_total[1] = fail ? 1u : 0u;
+        uvhttp_tls_send_summary_t sm;
+        memset(&sm, 0, sizeof(sm));
+        sm.out_bytes = t[1];
+        sm.n_records = t[0] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t[0];
+        sm.n_failed = fail ? a.n_sends : (uint32_t)t[2];
+        *a.summary = sm;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tls_send_write(PartsArgs a) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    const SendWork sw = s < a.n_sends ? a.sw[s] : SendWork{0, 0, 0, 0};
+    uint64_t tn, tb;
+    const uint64_t first = a.sblk[3 * blockIdx.x] + block_exclusive_sum<uint64_t>(sw.n_rec, &tn);
+    const uint64_t off = a.sblk[3 * blockIdx.x + 1] + block_exclusive_sum<uint64_t>(sw.bytes, &tb);
+    if (s >= a.n_sends) return;
+    const uvhttp_tls_send_t sd = a.sends[s];
+    uvhttp_tls_send_result_t r;
+    memset(&r, 0, sizeof(r));
+    r.next_seq = sd.seq;
+    r.status = sw.status;
+    if (a.n_total[1]) {  // capacity: no layout, nothing sealed
+        if (!sw.status) r.status = UVHTTP_TLS_REC_ERR_CAPACITY;
+        a.s_first[s] = 0;
+        a.s_out[s] = 0;
+    } else {
+        r.out_off = off;
+        r.out_len = sw.bytes;
+        r.next_seq = sd.seq + sw.n_rec;
+        r.first_record = (uint32_t)first;
+        r.n_records = (uint32_t)sw.n_rec;
+        r.plain_len = sw.bytes - sw.n_rec * sw.over;
+        a.s_first[s] = (uint32_t)first;
+        a.s_out[s] = off;
+    }
+    a.results[s] = r;
+}
+
+// the send of record r: the last one whose first_record <= r
+__device__ inline uint32_t send_of_record(const PartsArgs& a, uint32_t r) {
+    uint32_t lo = 0, hi = a.n_sends;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.s_first[mid] <= r) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one lane per record: its send, its part (the first one whose records, added to those of the
+// parts before it, pass the record's place in the send), its frame (the last one of the part's
+// run whose record prefix <= the place in the part's scan), its chunk
 __global__ __launch_bounds__(kBlock) void k_tls_parts_fill(PartsArgs a) {
     const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
     for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
-        uint32_t lo = 0, hi = a.n_sends;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (a.s_first[mid] <= r) lo = mid;
-            else hi = mid;
-        }
-        const uint32_t s = lo;
+        const uint32_t s = send_of_record(a, r);
         const uvhttp_tls_send_t sd = a.sends[s];
         const uint64_t k = r - a.s_first[s];
         uint64_t before = 0, plain = 0;  // records and frame bytes of the parts before the record's
@@ -2619,7 +2503,7 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_fill(PartsArgs a) {
                 continue;
             }
             const uint64_t pos = fr[first] + (k - before);
-            lo = first, hi = first + cnt;
+            uint32_t lo = first, hi = first + cnt;
             while (hi - lo > 1) {
                 const uint32_t mid = lo + (hi - lo) / 2;
                 if (fr[mid] <= pos) lo = mid;
@@ -2645,10 +2529,10 @@ __global__ __launch_bounds__(kBlock) void k_tls_parts_fill(PartsArgs a) {
 // ---- send side, a send's frames coalesced into full records (uvhttp_tls_gpu_seal_parts_coalesced) --
 //
 // A send's stream is its parts' runs back to back; a run without a bad frame is one contiguous
-// range of the arena, so the stream has at most 8 segments whatever the number of frames.  The
-// frame launches above give fr_bad (their record counts are not used), k_tls_coal_count makes a
-// send's segment table and its record and byte counts from at most 8 offset differences,
-// k_tls_send_scan / k_tls_send_write lay the sends out as they stand, k_tls_coal_fill writes a
+// range of the arena, so the stream has at most 8 segments whatever the number of frames.  Of the
+// plan above only (2) and (4) differ: the frame launches give fr_bad (their record counts are not
+// used), k_tls_coal_count makes a send's segment table beside send_count's walk and its records
+// from the stream's length, k_tls_send_scan / k_tls_send_write lay the sends out, k_tls_coal_fill writes a
 // record from closed-form arithmetic, k_tls_coal_gather copies every record's content to where its
 // ciphertext will lie (out + out_off + header), and the seal kernels run over records[] with
 // src = out, in place.
@@ -2672,74 +2556,30 @@ struct CoalArgs {
 
 constexpr uint32_t kGatherTile = 4096;  // record content bytes per workgroup pass: 16 per lane
 
+// a good run is segment p of the send's stream; the records follow from the stream's length
 __global__ __launch_bounds__(kBlock) void k_tls_coal_count(CoalArgs c) {
     const PartsArgs& a = c.p;
-    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-    uint64_t n_rec = 0, bytes = 0, failed = 0;
-    if (s < a.n_sends) {
-        const uvhttp_tls_send_t sd = a.sends[s];
-        CoalSeg* sg = c.seg + (uint64_t)UVHTTP_TLS_MAX_PARTS * s;
-        int32_t st = 0;
-        uint32_t over = 0;
-        if (sd.key >= a.n_keys || sd.key > 0xFFFFu || a.sched[sd.key].nr == 0) {
-            st = UVHTTP_TLS_REC_ERR_KEY;
-        } else {
-            uint64_t plain = 0;
-            for (uint32_t p = 0; p < a.n_parts; ++p) {
-                const uvhttp_tls_part_t& q = a.part[p];
-                uint32_t first, n;
-                parts_run(q, s, &first, &n);
-                const uint64_t last = (uint64_t)first + n;
-                const uint64_t fb = a.fbase[p];
-                if (last > q.n_frames || a.fr_bad[fb + last] != a.fr_bad[fb + first]) {
-                    st = UVHTTP_TLS_REC_ERR_RANGE;
-                    break;
-                }
-                // (no bad frame in the run: its offsets do not decrease and end within q.len)
-                uint64_t src = 0;
-                if (n) {
-                    const uint64_t b = q.frame_off[first];
-                    src = q.base + b;
-                    plain += q.frame_off[last] - b;
-                }
-                sg[p] = CoalSeg{src, plain};
-            }
-            if (!st) {
-                for (uint32_t p = a.n_parts; p < UVHTTP_TLS_MAX_PARTS; ++p) sg[p] = CoalSeg{0, plain};
-                const KeySched* k = a.sched + sd.key;
-                over = 5 + 16 + explicit_len(k->version, k->cipher) +
-                       (k->version == UVHTTP_TLS_VERSION_13 ? 1u : 0u);
-                n_rec = (plain + a.max_fragment - 1) / a.max_fragment;
-                bytes = plain + n_rec * over;
-            }
-        }
-        failed = st ? 1 : 0;
-        a.sw[s] = SendWork{n_rec, bytes, st, over};
-    }
-    uint64_t tn, tb, tf;
-    (void)block_exclusive_sum<uint64_t>(n_rec, &tn);
-    (void)block_exclusive_sum<uint64_t>(bytes, &tb);
-    (void)block_exclusive_sum<uint64_t>(failed, &tf);
-    if (threadIdx.x == 0) {
-        a.sblk[3 * blockIdx.x] = tn;
-        a.sblk[3 * blockIdx.x + 1] = tb;
-        a.sblk[3 * blockIdx.x + 2] = tf;
-    }
+    send_count(
+        a,
+        [&](uint32_t s, uint32_t p, uint32_t first, uint32_t last, uint64_t plain) {
+            const uvhttp_tls_part_t& q = a.part[p];
+            const uint64_t src = last > first ? q.base + q.frame_off[first] : 0;
+            c.seg[(uint64_t)UVHTTP_TLS_MAX_PARTS * s + p] = CoalSeg{src, plain};
+        },
+        [&](uint32_t s, uint64_t plain) {
+            for (uint32_t p = a.n_parts; p < UVHTTP_TLS_MAX_PARTS; ++p)
+                c.seg[(uint64_t)UVHTTP_TLS_MAX_PARTS * s + p] = CoalSeg{0, plain};
+            return (plain + a.max_fragment - 1) / a.max_fragment;
+        });
 }
 
-// one lane per record: its send (the last one whose first_record <= r); the rest is arithmetic,
-// every record of a send but the last holding max_fragment bytes
+// one lane per record: its send; the rest is arithmetic, every record of a send but the last
+// holding max_fragment bytes
 __global__ __launch_bounds__(kBlock) void k_tls_coal_fill(CoalArgs c) {
     const PartsArgs& a = c.p;
     const uint32_t n = a.n_total[0] < a.max_records ? a.n_total[0] : a.max_records;
     for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
-        uint32_t lo = 0, hi = a.n_sends;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (a.s_first[mid] <= r) lo = mid;
-            else hi = mid;
-        }
-        const uint32_t s = lo;
+        const uint32_t s = send_of_record(a, r);
         const uvhttp_tls_send_t sd = a.sends[s];
         const SendWork sw = a.sw[s];
         const KeySched* ks = a.sched + sd.key;
@@ -2871,14 +2711,14 @@ struct uvhttp_tls_gpu_engine {
     void* ws;
     size_t ws_bytes;
     uint32_t cap_keys, cap_streams, cap_records;
-    uint32_t cap_frames, cap_sends;  // seal_frames: frame scan entries, sends
+    uint32_t cap_frames, cap_sends;  // send plan: frame scan entries, sends
     KeySched* sched;
     RecWork* work;
     StreamWork* sw;
     uint64_t* blk;
     uint32_t* n_total;
     uint32_t* fix;
-    uint64_t* fr_rec;   // seal_frames scratch (SendArgs)
+    uint64_t* fr_rec;   // send plan scratch (PartsArgs)
     uint32_t* fr_bad;
     uint64_t* fblk;
     SendWork* send_work;
@@ -3031,6 +2871,135 @@ static void tls_timing_end(uvhttp_tls_gpu_engine_t* e, int k, hipStream_t s) {
     e->ev_used = k + 1;
 }
 
+// k_tls_seal / k_tls_seal_chacha over a record table of `count` entries: the grids from count,
+// capped (where a.n_total is given the kernels read their count from it)
+static void tls_launch_seal(uvhttp_tls_gpu_engine_t* e, const SealArgs& a, uint32_t count, hipStream_t s) {
+    const uint32_t need = (count + kCryptWaves - 1) / kCryptWaves;
+    const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
+    const int tk = tls_timing_begin(e, s);
+    const uint32_t need_s = (count + kOpenWaves - 1) / kOpenWaves;
+    const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
+    hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
+    hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
+    tls_timing_end(e, tk, s);
+}
+
+static void tls_launch_keys(uvhttp_tls_gpu_engine_t* e, const uvhttp_tls_key_t* keys, uint32_t n_keys,
+                            hipStream_t s) {
+    if (n_keys)
+        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
+}
+
+// A send call from its own argument checks to its first plan kernel: the part table into *p with
+// its bases (checked where bad_part, the text of that error, is given: seal_frames' one part is
+// the call's own), a zeroed summary for n_sends = 0 (the caller returns), the scratch (csends /
+// crecs: the coalesced call's), the ordering, the key schedules, the rest of *p.
+static int tls_send_begin(uvhttp_tls_gpu_engine_t* e, const char* bad_part, const uvhttp_tls_part_t* parts,
+                          uint32_t n_parts, uint64_t frames_len, const uvhttp_tls_send_t* sends,
+                          uint32_t n_sends, const uvhttp_tls_key_t* keys, uint32_t n_keys,
+                          uint32_t max_fragment, uvhttp_tls_seal_t* records, uint32_t max_records,
+                          uvhttp_tls_send_result_t* results, uvhttp_tls_send_summary_t* summary,
+                          uint64_t out_cap, uint32_t csends, uint32_t crecs, hipStream_t s, PartsArgs* p) {
+    memset(p, 0, sizeof(*p));
+    uint64_t n_frames_all = 0;
+    for (uint32_t k = 0; k < n_parts; ++k) {
+        const uvhttp_tls_part_t& q = parts[k];
+        if (bad_part &&
+            (!q.frame_off || !q.runs || ((uintptr_t)q.frame_off & 7u) || ((uintptr_t)q.runs & 3u) ||
+             q.run_stride < 8 || (q.run_stride & 3u) || q.base > frames_len || q.len > frames_len - q.base))
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, bad_part, hipSuccess);
+        n_frames_all += q.n_frames;
+        if (n_frames_all > (1u << 28))
+            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many frames", hipSuccess);
+        p->part[k] = q;
+        p->fbase[k + 1] = p->fbase[k] + q.n_frames + 1;
+        p->bbase[k + 1] = p->bbase[k] + (q.n_frames + 1 + kBlock - 1) / kBlock;
+    }
+    if (!n_sends) {
+        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
+        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
+        return UVHTTP_TLS_GPU_OK;
+    }
+    // the frame scratch holds every part's scan; a part's last workgroup may be partly empty
+    const int rc = tls_reserve(e, n_keys, 1, 1, p->fbase[n_parts] + UVHTTP_TLS_MAX_PARTS * kBlock, n_sends,
+                               csends, crecs);
+    if (rc) return rc;
+    tls_call_begin(e, s);
+    tls_launch_keys(e, keys, n_keys, s);
+    p->n_parts = n_parts;
+    p->max_fragment = max_fragment ? max_fragment : 16384u;
+    p->sends = sends;
+    p->n_sends = n_sends;
+    p->n_keys = n_keys;
+    p->sched = e->sched;
+    p->records = records;
+    p->max_records = max_records;
+    p->results = results;
+    p->summary = summary;
+    p->out_cap = out_cap;
+    p->fr_rec = e->fr_rec;
+    p->fr_bad = e->fr_bad;
+    p->fblk = e->fblk;
+    p->sw = e->send_work;
+    p->sblk = e->sblk;
+    p->s_first = e->s_first;
+    p->s_out = e->s_out;
+    p->n_total = e->n_total;
+    return UVHTTP_TLS_GPU_OK;
+}
+
+// pass (1) of the plan: every part's frame scan
+static void tls_launch_frame_scan(const PartsArgs& p, hipStream_t s) {
+    const uint32_t nfb = p.bbase[p.n_parts];
+    hipLaunchKernelGGL(k_tls_parts_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_scan, dim3(p.n_parts), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_tls_parts_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
+}
+
+// pass (3), after the call's count kernel
+static void tls_launch_send_scan(const PartsArgs& p, hipStream_t s) {
+    const uint32_t nsb = (p.n_sends + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, p, nsb);
+    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, p);
+}
+
+// the grid of a fill kernel: a lane per record of the table, capped
+static uint32_t tls_fill_grid(const uvhttp_tls_gpu_engine_t* e, uint32_t max_records) {
+    const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
+    const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
+    return need_f < cap_f ? need_f : cap_f;
+}
+
+static int tls_launched(uvhttp_tls_gpu_engine_t* e) {
+    const hipError_t h = hipGetLastError();
+    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
+    return UVHTTP_TLS_GPU_OK;
+}
+
+// seal_frames' and seal_parts' plan and seal: they differ in who made the part table
+static int tls_seal_parts(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames, uint64_t frames_len,
+                          const PartsArgs& p, uint8_t* out, hipStream_t s) {
+    const uint32_t nsb = (p.n_sends + kBlock - 1) / kBlock;
+    tls_launch_frame_scan(p, s);
+    hipLaunchKernelGGL(k_tls_parts_count, dim3(nsb), dim3(kBlock), 0, s, p);
+    tls_launch_send_scan(p, s);
+    if (p.max_records) {
+        hipLaunchKernelGGL(k_tls_parts_fill, dim3(tls_fill_grid(e, p.max_records)), dim3(kBlock), 0, s, p);
+        tls_launch_seal(e, SealArgs{frames, frames_len, p.records, p.max_records, out, p.out_cap, p.sched,
+                                    p.n_keys, e->te0, p.n_total},
+                        p.max_records, s);
+    }
+    return tls_launched(e);
+}
+
+// the no-engine answer of the send calls: there is no engine without a device
+static int tls_no_engine() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
+    return UVHTTP_TLS_GPU_EINVAL;
+}
+
 extern "C" {
 
 int uvhttp_tls_gpu_engine_create(int device, uvhttp_tls_gpu_engine_t** out) {
@@ -3132,9 +3101,7 @@ int uvhttp_tls_gpu_open_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* wire,
     a.fix = e->fix;
     a.te0 = e->te0;
     const uint32_t nb = (n_streams + kBlock - 1) / kBlock;
-    if (n_keys)
-        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
+    tls_launch_keys(e, keys, n_keys, s);
     hipLaunchKernelGGL(k_tls_walk_count, dim3(nb), dim3(kBlock), 0, s, a);
     hipLaunchKernelGGL(k_tls_walk_scan, dim3(1), dim3(kBlock), 0, s, a, nb);
     hipLaunchKernelGGL(k_tls_walk_write, dim3(nb), dim3(kBlock), 0, s, a);
@@ -3173,21 +3140,10 @@ int uvhttp_tls_gpu_seal_records(uvhttp_tls_gpu_engine_t* e, const uint8_t* src, 
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     tls_call_begin(e, s);
-    if (n_keys)
-        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
-    SealArgs a{src, src_len, recs, n_records, out, out_cap, e->sched, n_keys, e->te0, nullptr};
-    const uint32_t need = (n_records + kCryptWaves - 1) / kCryptWaves;
-    const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
-    const int tk = tls_timing_begin(e, s);
-    const uint32_t need_s = (n_records + kOpenWaves - 1) / kOpenWaves;
-    const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
-    hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
-    hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
-    tls_timing_end(e, tk, s);
-    const hipError_t h = hipGetLastError();
-    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_TLS_GPU_OK;
+    tls_launch_keys(e, keys, n_keys, s);
+    tls_launch_seal(e, SealArgs{src, src_len, recs, n_records, out, out_cap, e->sched, n_keys, e->te0, nullptr},
+                    n_records, s);
+    return tls_launched(e);
 }
 
 int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames, uint64_t frames_len,
@@ -3197,79 +3153,29 @@ int uvhttp_tls_gpu_seal_frames(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames
                                uvhttp_tls_seal_t* records, uint32_t max_records,
                                uvhttp_tls_send_result_t* results, uvhttp_tls_send_summary_t* summary,
                                uint8_t* out, uint64_t out_cap, void* stream) {
-    if (!e) {  // no engine: there is none without a device
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
-        return UVHTTP_TLS_GPU_EINVAL;
-    }
+    if (!e) return tls_no_engine();
     if ((!frames && frames_len) || (!frame_off && n_frames_total) || (!sends && n_sends) ||
         (!keys && n_keys) || (!records && max_records) || (!results && n_sends) || !summary ||
         (!out && out_cap) || max_fragment > 16384)
         return UVHTTP_TLS_GPU_EINVAL;
     if (n_sends > (1u << 26) || n_frames_total > (1u << 28) || max_records > (1u << 28))
         return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / frames / records", hipSuccess);
+    // one part: the whole buffer, the table as given (NULL with no frames: no kernel reads the
+    // offsets of a part without frames), the runs inside sends[]
+    uvhttp_tls_part_t one;
+    one.base = 0;
+    one.len = frames_len;
+    one.frame_off = frame_off;
+    one.runs = sends ? &sends->first_frame : nullptr;
+    one.run_stride = sizeof(uvhttp_tls_send_t);
+    one.n_frames = n_frames_total;
     DeviceGuard dev(e->device);
     hipStream_t s = (hipStream_t)stream;
-    if (!n_sends) {
-        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
-        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
-        return UVHTTP_TLS_GPU_OK;
-    }
-    int rc = tls_reserve(e, n_keys, 1, 1, n_frames_total + 1, n_sends);
-    if (rc) return rc;
-    tls_call_begin(e, s);
-    if (n_keys)
-        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
-    SendArgs p;
-    p.frame_off = frame_off;
-    p.frames_len = frames_len;
-    p.n_frames = n_frames_total;
-    p.max_fragment = max_fragment ? max_fragment : 16384u;
-    p.sends = sends;
-    p.n_sends = n_sends;
-    p.n_keys = n_keys;
-    p.sched = e->sched;
-    p.records = records;
-    p.max_records = max_records;
-    p.results = results;
-    p.summary = summary;
-    p.out_cap = out_cap;
-    p.fr_rec = e->fr_rec;
-    p.fr_bad = e->fr_bad;
-    p.fblk = e->fblk;
-    p.sw = e->send_work;
-    p.sblk = e->sblk;
-    p.s_first = e->s_first;
-    p.s_out = e->s_out;
-    p.n_total = e->n_total;
-    const uint32_t nfb = (n_frames_total + 1 + kBlock - 1) / kBlock;
-    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_tls_send_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_send_frame_scan, dim3(1), dim3(kBlock), 0, s, p, nfb);
-    hipLaunchKernelGGL(k_tls_send_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_send_count, dim3(nsb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, p, nsb);
-    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, p);
-    if (max_records) {
-        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
-        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
-        hipLaunchKernelGGL(k_tls_send_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, p);
-        // the seal kernels read their count from n_total[0]; grids from max_records, capped
-        SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
-                   e->n_total};
-        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
-        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
-        const int tk = tls_timing_begin(e, s);
-        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
-        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
-        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
-        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
-        tls_timing_end(e, tk, s);
-    }
-    const hipError_t h = hipGetLastError();
-    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_TLS_GPU_OK;
+    PartsArgs p;
+    const int rc = tls_send_begin(e, nullptr, &one, 1, frames_len, sends, n_sends, keys, n_keys, max_fragment,
+                                  records, max_records, results, summary, out_cap, 0, 0, s, &p);
+    if (rc || !n_sends) return rc;
+    return tls_seal_parts(e, frames, frames_len, p, out, s);
 }
 
 int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames, uint64_t frames_len,
@@ -3279,102 +3185,21 @@ int uvhttp_tls_gpu_seal_parts(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames,
                               uvhttp_tls_seal_t* records, uint32_t max_records,
                               uvhttp_tls_send_result_t* results, uvhttp_tls_send_summary_t* summary,
                               uint8_t* out, uint64_t out_cap, void* stream) {
-    if (!e) {  // no engine: there is none without a device
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
-        return UVHTTP_TLS_GPU_EINVAL;
-    }
+    if (!e) return tls_no_engine();
     if (!parts || n_parts == 0 || n_parts > UVHTTP_TLS_MAX_PARTS || (!frames && frames_len) ||
         (!sends && n_sends) || (!keys && n_keys) || (!records && max_records) || (!results && n_sends) ||
         !summary || (!out && out_cap) || max_fragment > 16384)
         return UVHTTP_TLS_GPU_EINVAL;
     if (n_sends > (1u << 26) || max_records > (1u << 28))
         return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many sends / records", hipSuccess);
-    PartsArgs p;
-    memset(&p, 0, sizeof(p));
-    uint64_t n_frames_all = 0;
-    for (uint32_t k = 0; k < n_parts; ++k) {
-        const uvhttp_tls_part_t& q = parts[k];
-        if (!q.frame_off || !q.runs || ((uintptr_t)q.frame_off & 7u) || ((uintptr_t)q.runs & 3u) ||
-            q.run_stride < 8 || (q.run_stride & 3u) || q.base > frames_len || q.len > frames_len - q.base)
-            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts: a part's pointers, stride or range", hipSuccess);
-        n_frames_all += q.n_frames;
-        if (n_frames_all > (1u << 28))
-            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many frames", hipSuccess);
-        p.part[k] = q;
-        p.fbase[k + 1] = p.fbase[k] + q.n_frames + 1;
-        p.bbase[k + 1] = p.bbase[k] + (q.n_frames + 1 + kBlock - 1) / kBlock;
-    }
     DeviceGuard dev(e->device);
     hipStream_t s = (hipStream_t)stream;
-    if (!n_sends) {
-        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
-        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
-        return UVHTTP_TLS_GPU_OK;
-    }
-    // the frame scratch holds every part's scan; a part's last workgroup may be partly empty
-    int rc = tls_reserve(e, n_keys, 1, 1, p.fbase[n_parts] + UVHTTP_TLS_MAX_PARTS * kBlock, n_sends);
-    if (rc) return rc;
-    tls_call_begin(e, s);
-    if (n_keys)
-        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
-    p.n_parts = n_parts;
-    p.max_fragment = max_fragment ? max_fragment : 16384u;
-    p.sends = sends;
-    p.n_sends = n_sends;
-    p.n_keys = n_keys;
-    p.sched = e->sched;
-    p.records = records;
-    p.max_records = max_records;
-    p.fr_rec = e->fr_rec;
-    p.fr_bad = e->fr_bad;
-    p.fblk = e->fblk;
-    p.sw = e->send_work;
-    p.sblk = e->sblk;
-    p.s_first = e->s_first;
-    p.s_out = e->s_out;
-    p.n_total = e->n_total;
-    SendArgs q;  // what k_tls_send_scan / k_tls_send_write read
-    memset(&q, 0, sizeof(q));
-    q.sends = sends;
-    q.n_sends = n_sends;
-    q.max_records = max_records;
-    q.results = results;
-    q.summary = summary;
-    q.out_cap = out_cap;
-    q.sw = e->send_work;
-    q.sblk = e->sblk;
-    q.s_first = e->s_first;
-    q.s_out = e->s_out;
-    q.n_total = e->n_total;
-    const uint32_t nfb = p.bbase[n_parts];
-    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_tls_parts_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_parts_frame_scan, dim3(n_parts), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_parts_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_parts_count, dim3(nsb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, q, nsb);
-    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, q);
-    if (max_records) {
-        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
-        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
-        hipLaunchKernelGGL(k_tls_parts_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, p);
-        // the seal kernels read their count from n_total[0]; grids from max_records, capped
-        SealArgs a{frames, frames_len, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
-                   e->n_total};
-        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
-        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
-        const int tk = tls_timing_begin(e, s);
-        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
-        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
-        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
-        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
-        tls_timing_end(e, tk, s);
-    }
-    const hipError_t h = hipGetLastError();
-    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_TLS_GPU_OK;
+    PartsArgs p;
+    const int rc = tls_send_begin(e, "seal_parts: a part's pointers, stride or range", parts, n_parts,
+                                  frames_len, sends, n_sends, keys, n_keys, max_fragment, records,
+                                  max_records, results, summary, out_cap, 0, 0, s, &p);
+    if (rc || !n_sends) return rc;
+    return tls_seal_parts(e, frames, frames_len, p, out, s);
 }
 
 int uvhttp_tls_gpu_seal_parts_coalesced(uvhttp_tls_gpu_engine_t* e, const uint8_t* frames,
@@ -3385,11 +3210,7 @@ int uvhttp_tls_gpu_seal_parts_coalesced(uvhttp_tls_gpu_engine_t* e, const uint8_
                                         uint32_t max_records, uvhttp_tls_send_result_t* results,
                                         uvhttp_tls_send_summary_t* summary, uint8_t* out,
                                         uint64_t out_cap, void* stream) {
-    if (!e) {  // no engine: there is none without a device
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UVHTTP_TLS_GPU_ENODEV;
-        return UVHTTP_TLS_GPU_EINVAL;
-    }
+    if (!e) return tls_no_engine();
     if (!parts || n_parts == 0 || n_parts > UVHTTP_TLS_MAX_PARTS || (!frames && frames_len) ||
         (!sends && n_sends) || (!keys && n_keys) || (!records && max_records) || (!results && n_sends) ||
         !summary || (!out && out_cap) || max_fragment > 16384)
@@ -3400,102 +3221,34 @@ int uvhttp_tls_gpu_seal_parts_coalesced(uvhttp_tls_gpu_engine_t* e, const uint8_
     if (frames_len && out_cap && (uintptr_t)out < (uintptr_t)frames + frames_len &&
         (uintptr_t)frames < (uintptr_t)out + out_cap)
         return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts_coalesced: out overlaps frames", hipSuccess);
-    CoalArgs c;
-    memset(&c, 0, sizeof(c));
-    PartsArgs& p = c.p;
-    uint64_t n_frames_all = 0;
-    for (uint32_t k = 0; k < n_parts; ++k) {
-        const uvhttp_tls_part_t& q = parts[k];
-        if (!q.frame_off || !q.runs || ((uintptr_t)q.frame_off & 7u) || ((uintptr_t)q.runs & 3u) ||
-            q.run_stride < 8 || (q.run_stride & 3u) || q.base > frames_len || q.len > frames_len - q.base)
-            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "seal_parts_coalesced: a part's pointers, stride or range",
-                           hipSuccess);
-        n_frames_all += q.n_frames;
-        if (n_frames_all > (1u << 28))
-            return tls_err(e, UVHTTP_TLS_GPU_EINVAL, "too many frames", hipSuccess);
-        p.part[k] = q;
-        p.fbase[k + 1] = p.fbase[k] + q.n_frames + 1;
-        p.bbase[k + 1] = p.bbase[k] + (q.n_frames + 1 + kBlock - 1) / kBlock;
-    }
     DeviceGuard dev(e->device);
     hipStream_t s = (hipStream_t)stream;
-    if (!n_sends) {
-        const hipError_t h = hipMemsetAsync(summary, 0, sizeof(*summary), s);
-        if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "memset summary", h);
-        return UVHTTP_TLS_GPU_OK;
-    }
-    // the frame scratch as in seal_parts; 8 x 16 bytes of segment table per send, 16 per record
-    int rc = tls_reserve(e, n_keys, 1, 1, p.fbase[n_parts] + UVHTTP_TLS_MAX_PARTS * kBlock, n_sends, n_sends,
-                         max_records);
-    if (rc) return rc;
-    tls_call_begin(e, s);
-    if (n_keys)
-        hipLaunchKernelGGL(k_tls_keys, dim3((n_keys + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                           keys, n_keys, (const uint32_t*)e->te0, e->sched);
-    p.n_parts = n_parts;
-    p.max_fragment = max_fragment ? max_fragment : 16384u;
-    p.sends = sends;
-    p.n_sends = n_sends;
-    p.n_keys = n_keys;
-    p.sched = e->sched;
-    p.records = records;
-    p.max_records = max_records;
-    p.fr_rec = e->fr_rec;
-    p.fr_bad = e->fr_bad;
-    p.fblk = e->fblk;
-    p.sw = e->send_work;
-    p.sblk = e->sblk;
-    p.s_first = e->s_first;
-    p.s_out = e->s_out;
-    p.n_total = e->n_total;
+    CoalArgs c;
+    // the scratch of seal_parts; 8 x 16 bytes of segment table per send, 16 per record
+    const int rc = tls_send_begin(e, "seal_parts_coalesced: a part's pointers, stride or range", parts, n_parts,
+                                  frames_len, sends, n_sends, keys, n_keys, max_fragment, records,
+                                  max_records, results, summary, out_cap, n_sends, max_records, s, &c.p);
+    if (rc || !n_sends) return rc;
     c.seg = e->coal_seg;
     c.crec = e->coal_rec;
-    SendArgs q;  // what k_tls_send_scan / k_tls_send_write read
-    memset(&q, 0, sizeof(q));
-    q.sends = sends;
-    q.n_sends = n_sends;
-    q.max_records = max_records;
-    q.results = results;
-    q.summary = summary;
-    q.out_cap = out_cap;
-    q.sw = e->send_work;
-    q.sblk = e->sblk;
-    q.s_first = e->s_first;
-    q.s_out = e->s_out;
-    q.n_total = e->n_total;
-    const uint32_t nfb = p.bbase[n_parts];
-    const uint32_t nsb = (n_sends + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_tls_parts_frame_count, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_parts_frame_scan, dim3(n_parts), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_parts_frame_write, dim3(nfb), dim3(kBlock), 0, s, p);
-    hipLaunchKernelGGL(k_tls_coal_count, dim3(nsb), dim3(kBlock), 0, s, c);
-    hipLaunchKernelGGL(k_tls_send_scan, dim3(1), dim3(kBlock), 0, s, q, nsb);
-    hipLaunchKernelGGL(k_tls_send_write, dim3(nsb), dim3(kBlock), 0, s, q);
+    tls_launch_frame_scan(c.p, s);
+    hipLaunchKernelGGL(k_tls_coal_count, dim3((n_sends + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c);
+    tls_launch_send_scan(c.p, s);
     if (max_records) {
-        const uint32_t need_f = (max_records + kBlock - 1) / kBlock;
-        const uint32_t cap_f = (uint32_t)e->crypt_grid * 4;
-        hipLaunchKernelGGL(k_tls_coal_fill, dim3(need_f < cap_f ? need_f : cap_f), dim3(kBlock), 0, s, c);
+        hipLaunchKernelGGL(k_tls_coal_fill, dim3(tls_fill_grid(e, max_records)), dim3(kBlock), 0, s, c);
         // the gather and the seal kernels read their count from n_total[0] (0 on a capacity
         // failure: nothing is gathered either); grids from max_records, capped
         GatherArgs g{frames, frames_len, out, records, max_records,
-                     (p.max_fragment + kGatherTile - 1) / kGatherTile, e->coal_seg, e->coal_rec, e->n_total};
+                     (c.p.max_fragment + kGatherTile - 1) / kGatherTile, e->coal_seg, e->coal_rec, e->n_total};
         const uint64_t need_g = (uint64_t)max_records * g.tiles_per_rec;
         const uint64_t cap_g = (uint64_t)e->crypt_grid * 8;
         hipLaunchKernelGGL(k_tls_coal_gather, dim3((uint32_t)(need_g < cap_g ? need_g : cap_g)), dim3(kBlock), 0, s, g);
         // in place: a record's content lies at out + src_off = out + out_off + header
-        SealArgs a{out, out_cap, records, max_records, out, out_cap, e->sched, n_keys, e->te0, e->n_total};
-        const uint32_t need = (max_records + kCryptWaves - 1) / kCryptWaves;
-        const uint32_t grid = need < (uint32_t)e->crypt_grid ? need : (uint32_t)e->crypt_grid;
-        const int tk = tls_timing_begin(e, s);
-        const uint32_t need_s = (max_records + kOpenWaves - 1) / kOpenWaves;
-        const uint32_t cap_s = (uint32_t)e->crypt_grid * kCryptWaves / kOpenWaves;
-        hipLaunchKernelGGL(k_tls_seal, dim3(need_s < cap_s ? need_s : cap_s), dim3(kOpenWG), 0, s, a);
-        hipLaunchKernelGGL(k_tls_seal_chacha, dim3(grid), dim3(kCryptWG), 0, s, a);
-        tls_timing_end(e, tk, s);
+        tls_launch_seal(e, SealArgs{out, out_cap, records, max_records, out, out_cap, e->sched, n_keys, e->te0,
+                                    e->n_total},
+                        max_records, s);
     }
-    const hipError_t h = hipGetLastError();
-    if (h != hipSuccess) return tls_err(e, UVHTTP_TLS_GPU_ELAUNCH, "launch", h);
-    return UVHTTP_TLS_GPU_OK;
+    return tls_launched(e);
 }
 
 int uvhttp_tls_gpu_ws_streams(uvhttp_tls_gpu_engine_t* e, const uvhttp_tls_result_t* results,
