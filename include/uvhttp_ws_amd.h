@@ -1473,7 +1473,10 @@ int uvhttp_ws_gpu_pipeline_wait_compact(uvhttp_ws_gpu_pipeline_t* p, int slot, c
  * state = CLOSED for CLOSE, control-sink echo / pong when conn->user_data != NULL.  `wire`
  * is the host copy of the decoded wire (slot buffer).  Frames [0, summary->n_delivered) are
  * delivered; returns UVHTTP_OK, or UVHTTP_ERROR_INVALID_PARAM if the batch failed (after
- * delivering the frames before the failure, like process_data). */
+ * delivering the frames before the failure, like process_data).  `desc` holds the batch's
+ * n_frames entries: when the failing frame, desc[n_delivered], is a first fragment that crossed
+ * max_message_size, conn->fragmented_opcode takes its opcode, as the reference sets it before
+ * it measures the fragment (src/uvhttp_websocket.c:972-980). */
 uvhttp_error_t uvhttp_ws_deliver_batch(struct uvhttp_ws_connection* conn, const uint8_t* wire,
                                        const uvhttp_ws_frame_desc_t* desc,
                                        const uvhttp_ws_batch_summary_t* summary);
@@ -1500,8 +1503,9 @@ uvhttp_error_t uvhttp_ws_deliver_batch(struct uvhttp_ws_connection* conn, const 
  *   frame_stride (a caller may copy back just those frame_stride bytes into a buffer it
  *   offsets accordingly).  Reserved opcodes 3-7 / 11-15 are delivered without a callback, as
  *   the reference ignores them.  Returns UVHTTP_OK, or UVHTTP_ERROR_INVALID_PARAM if the batch
- *   failed (after delivering the frames before the failure, like process_data) or the
- *   arguments cannot describe the batch. */
+ *   failed (after delivering the frames before the failure, like process_data; with descriptors
+ *   a failing first fragment leaves its opcode in conn->fragmented_opcode as in
+ *   uvhttp_ws_deliver_batch) or the arguments cannot describe the batch. */
 uvhttp_error_t uvhttp_ws_deliver_messages(struct uvhttp_ws_connection* conn, const uint8_t* arena,
                                           const uvhttp_ws_message_desc_t* msgs,
                                           const uvhttp_ws_batch_summary_t* summary,

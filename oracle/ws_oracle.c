@@ -7,10 +7,11 @@
  * bench.py's cpu_baseline leg may load it.  The product library (uvhttp_amd/) never
  * links, loads or calls anything in this directory.
  *
- * Pinning: the reference cannot be built in this image without writing stand-in headers
- * for mbedtls/llhttp/uthash (absent, un-vendored submodules), so it is treated as
- * unbuildable.  This restatement is pinned instead by the
- * known-answer vectors held in the reference's own unit tests, transcribed as data into
+ * Pinning: the reference's own unit is built beside this file (ref.mk -> _ref/libws_ref.so, driven
+ * by ref_driver.c) and tests/test_reference_diff.py runs the two against each other; the committed
+ * transcripts (tests/golden/reference_transcripts.json) hold its results where the reference tree
+ * is not at hand.  The restatement is also pinned by the known-answer vectors held
+ * in the reference's own unit tests, transcribed as data into
  * tests/golden/reference_known_answers.json and checked by tests/test_oracle_golden.py.
  *
  * Restated functions (each follows the cited reference lines statement by statement):

@@ -56,13 +56,18 @@ def test_no_gpu_means_enodev():
 
 
 def test_product_does_not_reference_oracle():
-    """The product library and package never load the oracle (no CPU fallback path)."""
+    """The product library and package never load the oracle (no CPU fallback path), nor the
+    reference build beside it (oracle/_ref/libws_ref.so and its driver's ws_ref_* calls)."""
     for p in glob.glob(os.path.join(REPO, "uvhttp_amd", "**", "*"), recursive=True):
-        if os.path.isfile(p) and p.endswith((".py", ".c", ".hip", ".h")):
+        if os.path.isfile(p) and p.endswith((".py", ".c", ".cpp", ".hip", ".h")):
             txt = open(p).read()
             assert "libws_oracle" not in txt and "import _oracle" not in txt, p
-    blob = open(U.LIB_PATH, "rb").read()
-    assert b"libws_oracle" not in blob and b"oracle_" not in blob
+            assert "oracle/_ref" not in txt and "libws_ref" not in txt and "ws_ref_" not in txt, p
+            assert "import _reference" not in txt, p
+    for path in (U.LIB_PATH, U.TESTHOOKS_LIB_PATH):
+        blob = open(path, "rb").read()
+        assert b"libws_oracle" not in blob and b"oracle_" not in blob, path
+        assert b"oracle/_ref" not in blob and b"libws_ref" not in blob and b"ws_ref_" not in blob, path
 
 
 def test_fault_injection_only_in_the_test_build():

@@ -326,6 +326,26 @@ uvhttp_error_t uvhttp_ws_process_data(struct uvhttp_ws_connection* c, const uint
 
 /* ---- delivery of a device-decoded batch (include/uvhttp_ws_amd.h) ----------------------- */
 
+/* What the frame that failed a batch left behind in the reference: a first fragment (TEXT /
+ * BINARY, FIN clear, no message open) records its opcode and zeroes the fragment sizes BEFORE
+ * uvhttp_ws_fragment_append measures it against max_message_size (src/uvhttp_websocket.c:972-980),
+ * so a start that fails that check still changes fragmented_opcode.  Every other failure returns
+ * before it writes anything. */
+static void failed_start_keeps_its_opcode(uvhttp_ws_connection_t* c,
+                                          const uvhttp_ws_batch_summary_t* summary,
+                                          const uvhttp_ws_frame_desc_t* failing) {
+    if (summary->first_status != UVHTTP_WS_FRAME_ERR_MESSAGE || failing == NULL ||
+        c->fragmented_message != NULL)
+        return;
+    const int opcode = failing->opcode & 0x0F;
+    if ((opcode != UVHTTP_WS_OPCODE_TEXT && opcode != UVHTTP_WS_OPCODE_BINARY) ||
+        (failing->flags & UVHTTP_WS_FLAG_FIN))
+        return;
+    c->fragmented_opcode = (uvhttp_ws_opcode_t)opcode;
+    c->fragmented_size = 0;
+    c->fragmented_capacity = 0;
+}
+
 uvhttp_error_t uvhttp_ws_deliver_batch(struct uvhttp_ws_connection* c, const uint8_t* wire,
                                        const uvhttp_ws_frame_desc_t* desc,
                                        const uvhttp_ws_batch_summary_t* summary) {
@@ -342,6 +362,8 @@ uvhttp_error_t uvhttp_ws_deliver_batch(struct uvhttp_ws_connection* c, const uin
         const uint8_t* payload = d->payload_len ? wire + d->payload_off : NULL;
         if (dispatch_frame(c, &h, payload) != 0) return UVHTTP_ERROR_INVALID_PARAM;
     }
+    if (summary->status != 0 && desc != NULL && summary->n_delivered < summary->n_frames)
+        failed_start_keeps_its_opcode(c, summary, &desc[summary->n_delivered]);
     return summary->status == 0 ? UVHTTP_OK : UVHTTP_ERROR_INVALID_PARAM;
 }
 
@@ -383,6 +405,7 @@ uvhttp_error_t uvhttp_ws_deliver_messages(struct uvhttp_ws_connection* c, const 
     /* summary-only: only the last delivered frame can be a non-data frame (frames of a
      * >= 140-byte stride are too long to be control frames); find out whether it is one */
     const uint8_t* last_ctl = NULL;
+    int last_start = 0; /* the last frame is an empty first fragment: its opcode */
     uvhttp_ws_frame_header_t lh;
     size_t lhead = 0;
     if (desc == NULL && nd > 0) {
@@ -394,8 +417,12 @@ uvhttp_error_t uvhttp_ws_deliver_messages(struct uvhttp_ws_connection* c, const 
             last_ctl = wire + (size_t)last * frame_stride;
             if (uvhttp_ws_parse_frame_header(last_ctl, (size_t)frame_stride, &lh, &lhead) != UVHTTP_OK)
                 return UVHTTP_ERROR_INVALID_PARAM;
-            if (lh.opcode < UVHTTP_WS_OPCODE_CLOSE) last_ctl = NULL; /* a data frame that completes
-                                                                      nothing: a zero-length start */
+            if (lh.opcode < UVHTTP_WS_OPCODE_CLOSE) { /* a data frame that completes nothing: a
+                                                         zero-length start (or empty middle fragment) */
+                last_ctl = NULL;
+                if ((lh.opcode == UVHTTP_WS_OPCODE_TEXT || lh.opcode == UVHTTP_WS_OPCODE_BINARY) && !lh.fin)
+                    last_start = lh.opcode;
+            }
         }
     }
     if (desc != NULL && nd > 0 && wire == NULL) {
@@ -422,6 +449,21 @@ uvhttp_error_t uvhttp_ws_deliver_messages(struct uvhttp_ws_connection* c, const 
                           msgs[m].opcode);
     if (last_ctl != NULL)
         dispatch_control(c, lh.opcode, last_ctl + lhead + (lh.mask ? 4u : 0u), lh.payload_length);
+    /* fragmented_opcode is what the last first fragment wrote there: the reference sets it when a
+     * TEXT / BINARY frame with FIN clear arrives and no message is open (:972) and never clears
+     * it, so it outlives the message; a zero-length first fragment writes it too */
+    if (desc != NULL) {
+        for (uint32_t i = 0; i < nd; ++i)
+            if ((desc[i].opcode == UVHTTP_WS_OPCODE_TEXT || desc[i].opcode == UVHTTP_WS_OPCODE_BINARY) &&
+                !(desc[i].flags & UVHTTP_WS_FLAG_FIN))
+                c->fragmented_opcode = (uvhttp_ws_opcode_t)desc[i].opcode;
+    } else { /* summary-only: a message of several frames began with such a fragment, and only the
+                last frame can be an empty one (every other fills its >= 140-byte slot) */
+        for (uint32_t k = 0; k < nm; ++k)
+            if (msgs[k].first_frame != msgs[k].last_frame)
+                c->fragmented_opcode = (uvhttp_ws_opcode_t)msgs[k].opcode;
+        if (last_start) c->fragmented_opcode = (uvhttp_ws_opcode_t)last_start;
+    }
     if (open) { /* the open message as append_fragment left it: capacity = first fragment
                    doubled until it holds everything appended (src/uvhttp_websocket.c:794-816) */
         const uvhttp_ws_message_desc_t* d = &msgs[nm];
@@ -438,6 +480,8 @@ uvhttp_error_t uvhttp_ws_deliver_messages(struct uvhttp_ws_connection* c, const 
         c->fragmented_capacity = cap;
         c->fragmented_opcode = (uvhttp_ws_opcode_t)d->opcode;
     }
+    if (summary->status != 0 && desc != NULL && nd < summary->n_frames)
+        failed_start_keeps_its_opcode(c, summary, &desc[nd]);
     return summary->status == 0 ? UVHTTP_OK : UVHTTP_ERROR_INVALID_PARAM;
 }
 
